@@ -5,10 +5,12 @@ import re, subprocess, sys, tempfile, os
 src = sys.argv[1]
 flags = [a for a in sys.argv[2:] if a.startswith("-")]
 filt = [a for a in sys.argv[2:] if not a.startswith("-")]
-out = os.path.join(tempfile.gettempdir(), os.path.basename(src) + ".s")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", out, src] + flags,
-                      stderr=subprocess.DEVNULL)
-txt = open(out).read()
+# a directory of this run's own: a fixed name under the shared temp directory may belong to another user or another run
+with tempfile.TemporaryDirectory() as tmp:
+    out = os.path.join(tmp, os.path.basename(src) + ".s")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", out, src] + flags,
+                          stderr=subprocess.DEVNULL)
+    txt = open(out).read()
 meta = txt[txt.index("amdhsa.kernels:"):]
 rows = []
 for blk in meta.split("  - .agpr_count:")[1:]:

@@ -5,10 +5,10 @@ set -o pipefail
 R=$PWD
 OUT=$R/gpurun_out/refresh4
 mkdir -p $OUT
-python bench.py > $OUT/bench_sample.json 2> $OUT/bench_sample.err
+python bench.py --full > $OUT/bench_sample.json 2> $OUT/bench_sample.err
 echo "bench done rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-configs > /dev/null 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-configs > /dev/null 2>&1
 echo "trace done rc=$?"
 cd $R
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats.csv; rm -rf $OUT/trace

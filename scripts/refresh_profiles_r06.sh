@@ -9,13 +9,13 @@ mkdir -p $OUT
 SECTIONS=${@:-bench trace pmc pmcbusy rig rigtrace surface}
 has() { [[ " $SECTIONS " == *" $1 "* ]]; }
 if has bench; then
-  python bench.py > $OUT/bench_sample.json 2> $OUT/bench_sample.err
+  python bench.py --full > $OUT/bench_sample.json 2> $OUT/bench_sample.err
   echo "bench done rc=$?"
 fi
 if has trace; then
   # the bench LOOP's process only: no class-surface children, no rig configurations, no CPU leg
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-configs --no-class-surface > $OUT/trace_bench_line.json 2> /dev/null
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-configs --no-class-surface > $OUT/trace_bench_line.json 2> /dev/null
   echo "trace done rc=$?"
   cd $R
   cp "$(python scripts/pick_kernel_stats.py $OUT/trace k_intr_persist)" $OUT/kernel_stats.csv && rm -rf $OUT/trace

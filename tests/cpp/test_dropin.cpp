@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "calibrator.hh"
 #include "data_generator.hh"
 #include "extrinsics_calibrator.hh"
@@ -110,6 +112,19 @@ static void single_camera() {
 }
 
 // ---- 2. two-camera rig ---------------------------------------------------------------------------
+// a directory of this run's own under $TMPDIR (default /tmp): a fixed file name there may belong to another user or run
+static std::string private_tmp_dir() {
+  const char* t = std::getenv("TMPDIR");
+  std::string tmpl = std::string(t && *t ? t : "/tmp") + "/cc_dropin_XXXXXX";
+  std::vector<char> buf(tmpl.begin(), tmpl.end());
+  buf.push_back('\0');
+  if (!mkdtemp(buf.data())) {
+    std::perror("mkdtemp");
+    std::exit(2);
+  }
+  return buf.data();
+}
+
 static void rig() {
   const int num_cams = 2, num_frames = 200, pts_per_frame = 4;   // the reference uses 1000 frames (:57)
   std::mt19937 gen(0);
@@ -154,7 +169,8 @@ static void rig() {
       }
     }
   }
-  const std::string fname = "/tmp/cc_dropin_rig.json";
+  const std::string dir = private_tmp_dir();
+  const std::string fname = dir + "/cc_dropin_rig.json";
   calib.Serialize(fname);                                                                        // :136-139
   // Parse into the SAME object appends the cameras again and rebuilds the frozen set from the parsed
   // ones only (the reference does not clear camera_T_rigs_, extrinsics_calibrator.cpp:349-351): kept.
@@ -188,11 +204,14 @@ static void rig() {
   CHECK(calib.NumWorldPoints() == (size_t)((num_frames - 3) * pts_per_frame));
   // ... and the solve of what is left is the solve of the same data read into a fresh object (the class keeps the world points
   // flat by global id, which a removal invalidates; the JSON numbers are shortest round-trip)
-  const std::string fname2 = "/tmp/cc_dropin_rig_removed.json";
+  const std::string fname2 = dir + "/cc_dropin_rig_removed.json";
   calib.Serialize(fname2);
   ExtrinsicsCalibrator fresh;
   fresh.SetVerbose(false);
   fresh.Parse(fname2);
+  std::remove(fname.c_str());
+  std::remove(fname2.c_str());
+  rmdir(dir.c_str());
   calib.Optimize();
   fresh.Optimize();
   CHECK(calib.LastStatus() == 0 && fresh.LastStatus() == 0);

@@ -37,6 +37,27 @@ def test_committed_sample_line_has_every_contract_field():
     assert d["configs"]["rig_c4_poses"]["dominant_kernel"]["bound"] == "latency"
 
 
+def test_dumped_outputs_are_float64_and_capped_at_64_mib(tmp_path):
+    """--dump-outputs: every array float64; per-frame arrays beyond the 64 MiB budget become a fixed, seeded sample of frames."""
+    import numpy as np
+    import bench
+    n = 1_300_000   # 7 doubles per frame: 72.8 MB in all
+    arrays = {"intrinsics": np.arange(9.0), "frame_quaternions": np.ones((n, 4), dtype=np.float32), "frame_translations": np.zeros((n, 3)),
+              "solve_summary": np.array([4, 2.0, 1.0])}
+    got = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.write_outputs(str(d), arrays)
+        got.append({p.stem: np.load(p) for p in d.iterdir()})
+    a, b = got
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20 and all(x.dtype == np.float64 for x in a.values())
+    idx = a["frame_index"].astype(np.int64)
+    assert len(idx) == len(a["frame_quaternions"]) == len(a["frame_translations"]) > n // 2 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a["intrinsics"], arrays["intrinsics"]) and np.array_equal(a["solve_summary"], arrays["solve_summary"])
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    bench.write_outputs(str(tmp_path / "small"), {"intrinsics": np.arange(9.0), "frame_translations": np.zeros((1000, 3))})
+    assert sorted(p.name for p in (tmp_path / "small").iterdir()) == ["frame_translations.npy", "intrinsics.npy"]
+
+
 def test_bench_refuses_to_run_without_a_gpu():
     import torch
     if torch.cuda.is_available():

@@ -18,10 +18,12 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _run(extra_env, frames, bare=False):
+def _run(extra_env, frames, bare=False, full=False):
     env = dict(os.environ, CC_BENCH_DEVICE="0", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                GPU_MAX_HW_QUEUES="8", **extra_env)
     bench = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "4", "--frames", str(frames), "--points", "120"]
+    if full:   # the strong-scaling leg and the convergence report run with --full only
+        bench.append("--full")
     if bare:   # the driver's one-GPU command shape with N = 2: no launcher in front, no WORLD_SIZE -- bench.py starts its ranks itself
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
             env.pop(k, None)
@@ -38,7 +40,7 @@ def _run(extra_env, frames, bare=False):
 
 @pytest.mark.gpu
 def test_two_rank_bench_line_over_the_mailbox_exchange():
-    d = _run({"CC_EXCHANGE": "mailbox"}, 60)
+    d = _run({"CC_EXCHANGE": "mailbox"}, 60, full=True)
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["warmup"] == 4 and d["scaling"] == "weak"
     assert d["config"]["exchange"] == "mailbox" and d["config"]["frames_total"] == 120
     assert d["value"] > 0 and abs(d["value"] - 2 * d["config"]["observations_total"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
@@ -57,6 +59,6 @@ def test_two_rank_bench_line_as_independent_replicas():
 
 @pytest.mark.gpu
 def test_bare_command_starts_two_ranks_by_itself():
-    d = _run({"CC_EXCHANGE": "mailbox"}, 40, bare=True)
+    d = _run({"CC_EXCHANGE": "mailbox"}, 40, bare=True, full=True)
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["config"]["exchange"] == "mailbox" and d["config"]["frames_total"] == 80
     assert [r["rank"] for r in d["config"]["ranks"]] == [0, 1] and d["value"] > 0 and d["strong_scaling"]["value"] > 0
