@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "cc_rig_get_state", "cc_rig_solver_form", "cc_rig_solver_status", "cc_rig_eval", "cc_rig_optimize", "cc_rig_comm_init", "cc_rig_exchange_export", "cc_rig_exchange_attach", "cc_rigk_create",
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
     "cc_rigk_get_camera_intrinsics", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
+    "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
 ]
 # every symbol include/cc_harness.h declares (synthetic-input harness, host code)
 HARNESS_SYMBOLS = [
@@ -559,6 +560,24 @@ class RigProblem:
         c = C.c_double()
         _check(lib().cc_rig_eval(self._h, C.byref(c)))
         return c.value
+
+    def set_inner_iterations(self, enable=True, tolerance=1e-3):
+        """Ceres' inner iterations for later solves (cc_rig_set_inner_iterations; poses only, one device, off by default)."""
+        _check(lib().cc_rig_set_inner_iterations(self._h, C.c_int32(1 if enable else 0), C.c_double(tolerance)))
+
+    def inner_pass(self):
+        """One inner pass from the current state (cc_rig_inner_pass): (cost_before, cost_after, mini_iterations[4])."""
+        c0, c1 = C.c_double(), C.c_double()
+        it = (C.c_int32 * 4)()
+        _check(lib().cc_rig_inner_pass(self._h, C.byref(c0), C.byref(c1), it))
+        return c0.value, c1.value, [int(v) for v in it]
+
+    def inner_status(self):
+        """The last solve's inner iterations (cc_rig_inner_status): dict of passes, useful_passes, enabled_at_end, cost_removed."""
+        p, u, e = C.c_int32(), C.c_int32(), C.c_int32()
+        r = C.c_double()
+        _check(lib().cc_rig_inner_status(self._h, C.byref(p), C.byref(u), C.byref(e), C.byref(r)))
+        return dict(passes=p.value, useful_passes=u.value, enabled_at_end=e.value, cost_removed=r.value)
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))

@@ -175,6 +175,8 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("SetDevices", &ExtrinsicsCalibrator::SetDevices, py::arg("devices"))
       .def("SetVerbose", &ExtrinsicsCalibrator::SetVerbose, py::arg("verbose"))
       .def("LastStatus", &ExtrinsicsCalibrator::LastStatus)
+      .def("SetInnerIterations", &ExtrinsicsCalibrator::SetInnerIterations, py::arg("enable"))
+      .def("LastInnerPasses", &ExtrinsicsCalibrator::LastInnerPasses)
       .def("LastIterations", &ExtrinsicsCalibrator::LastIterations)
       .def("LastSolverReruns", &ExtrinsicsCalibrator::LastSolverReruns)
       .def("LastSolverForm", &ExtrinsicsCalibrator::LastSolverForm)

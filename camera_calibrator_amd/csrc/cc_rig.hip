@@ -44,6 +44,7 @@
 #include <mutex>
 #include "cc_device.hpp"
 #include "cc_persist_dev.hpp"
+#include "cc_rig_inner.hpp"
 
 namespace cc {
 
@@ -376,6 +377,12 @@ struct cc_rig {
   std::vector<int> event_kind;
   std::vector<int> event_round;   // round of the solve a probed launch belongs to (summarise_probes)
   int enq_round = 0;
+  // inner iterations (cc_rig_set_inner_iterations; cc_rig_inner.hpp)
+  bool inner_on = false;
+  double inner_tol = 1e-3;
+  double* d_inner = nullptr;       // [RIG_IN_WORDS] device state of the outer-loop hook
+  int32_t* d_inner_it = nullptr;   // [2C + 2F] mini-solve iterations per block of the last pass
+  double inner_init[cc::RIG_IN_WORDS] = {};   // what a solve starts the device state from (source of an asynchronous copy)
 };
 
 namespace cc {
@@ -809,13 +816,24 @@ static int rig_size_reduce_grid(cc_rig* h) {
   return 0;
 }
 
+static RigInnerDev rig_inner_dev(const cc_rig* h) {
+  const RigDev& d = h->d;
+  return RigInnerDev{d.F, d.NG, d.C, d.fmode, d.uv, d.oxyz, d.goff, d.gframe, d.gcam, d.fgoff, d.cam_goff, d.cam_glist, d.pcol,
+                     d.cam, d.pose, d.camrec, d.frec, d.gstats, d.ctl, d.ctl_next, d.opts, d.log, d.log_cap, d.huber_a,
+                     h->d_inner, h->d_inner_it};
+}
+static int rig_inner_alloc(cc_rig* h) {
+  if (h->d_inner) return 0;
+  if (int rc = dev_zeroed(h, &h->d_inner, RIG_IN_WORDS)) return rc;
+  return dev_zeroed(h, &h->d_inner_it, (size_t)(2 * h->C + 2 * h->F));
+}
 // One round: sweep -> [statistics exchange] -> [init, first round only] -> decision + elimination ->
 // reduce + solve step -> pose update (what the next round's sweep evaluates). The first round of a solve is
 // the initial evaluation.
 static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish = false) {
   const RigDev& d = h->d;
   struct RoundCount { cc_rig* h; ~RoundCount() { h->enq_round++; } } count_round{h};
-  { RigProbe p(h, CC_K_SWEEP, profile);
+  auto sweep = [&]() {
     if (d.kcm) hipLaunchKernelGGL(k_rig_sweep_k2, dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);   // (a workgroup of two waves per group)
     else if (d.kmode && h->sweep_waves == 1) hipLaunchKernelGGL(k_rig_sweep_adjk<1>, dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
     else if (d.kmode) hipLaunchKernelGGL(k_rig_sweep_adjk<4>, dim3((unsigned)h->NG), dim3(256), 0, h->stream, d);
@@ -833,7 +851,17 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     }
     else if (h->sweep_waves == 4) hipLaunchKernelGGL((k_rig_sweep_adj<4>), dim3((unsigned)h->NG), dim3(256), 0, h->stream, d);
     else if (h->sweep_waves == 2) hipLaunchKernelGGL((k_rig_sweep_adj<2>), dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);
-    else hipLaunchKernelGGL((k_rig_sweep_adj<1>), dim3((unsigned)h->NG), dim3(64), 0, h->stream, d); }
+    else hipLaunchKernelGGL((k_rig_sweep_adj<1>), dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
+  };
+  { RigProbe p(h, CC_K_SWEEP, profile); sweep(); }
+  if (h->inner_on && !initial && !h->comm && !h->exchange) {
+    // inner iterations (cc_rig_inner.hpp): a pass on the candidate, the sweep again at its result, the decision with the
+    // augmented model. Every launch returns at once in a round without a pass; none is probed (kept out of kernel_ms).
+    const RigInnerDev I = rig_inner_dev(h);
+    rig_inner_enqueue_before_sweep(I, h->stream);
+    sweep();
+    rig_inner_enqueue_decide(I, h->stream);
+  }
   if (h->comm || h->exchange) {
     { RigProbe p(h, CC_K_DECIDE, profile); hipLaunchKernelGGL(k_rig_stats, dim3(1), dim3(256), 0, h->stream, d); }
     if (h->comm) { RigProbe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec_stats, 4 + d.S, h->stream)) return rc; }
@@ -1506,6 +1534,12 @@ static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
   // fresh control block (both copies) and synchronisation words -- counters, flag word, failure word: a failed solve may
   // have left any of them behind -- in ONE fill (they are one piece of memory, rig_create_impl)
   CC_HIP(hipMemsetAsync(h->d.ctl, 0, 2 * sizeof(LmCtl) + 16 * sizeof(unsigned), h->stream));
+  if (h->inner_on) {   // inner iterations enabled again at the start of every solve, statistics from zero
+    for (double& v : h->inner_init) v = 0.0;
+    h->inner_init[RIG_IN_ENABLED] = 1.0;
+    h->inner_init[RIG_IN_TOL] = h->inner_tol;
+    CC_HIP(hipMemcpyAsync(h->d_inner, h->inner_init, sizeof(h->inner_init), hipMemcpyHostToDevice, h->stream));
+  }
   for (auto e : h->events) hipEventDestroy(e);
   h->events.clear();
   h->event_kind.clear();
@@ -1517,7 +1551,7 @@ static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
 
 static int rig_launch(cc_rig* h, RigRun* r, int chunk) {
   CC_HIP(hipSetDevice(h->device));
-  if (chunk == 0 && !r->no_persist && h->persist_w_ok && !r->profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1) {
+  if (chunk == 0 && !r->no_persist && h->persist_w_ok && !h->inner_on && !r->profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1) {
     // the whole solve in one launch (k_rig_persist); the control workgroup publishes when it is over
     RigPersistDev q = h->pq;
     q.max_rounds = r->o.max_iterations + 2;
@@ -1691,7 +1725,7 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
   // What the DEVICE has said about lean solves lately (persist_device_try, cc_common.hpp): a one-shot caller's handle is new
   // every call, so after a give-up the device's back-off window -- not this handle's memory -- keeps the next solves on the
   // three-kernel form; one solve probes the lean form again when the window is over.
-  const bool lean_wanted = h->persist_w_ok && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1;
+  const bool lean_wanted = h->persist_w_ok && !h->inner_on && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1;
   bool lean_tried = false;
   if (lean_wanted) {
     lean_tried = persist_device_try(h->device, 1);
@@ -1701,7 +1735,7 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
   // process -- persist_mutex, cc_common.hpp; a second host thread waits here instead of inside a kernel for 1.3 s)
   std::unique_lock<std::mutex> lean_lock(persist_mutex(h->device), std::defer_lock);
   for (int chunk = 0;; ++chunk) {
-    if (chunk == 0 && !r.no_persist && h->persist_w_ok && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)
+    if (chunk == 0 && !r.no_persist && h->persist_w_ok && !h->inner_on && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)
       lean_lock.lock();
     if (int rc = rig_launch(h, &r, chunk)) {
       if (chunk == 0 && lean_tried) persist_device_gave_up(h->device, 1);   // (a probe that never started is over too)
@@ -1751,7 +1785,7 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
 int cc_rig_solver_form(cc_rig* h) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_solver_form: NULL handle");
-  if (!(h->persist_w_ok && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)) return 0;
+  if (!(h->persist_w_ok && !h->inner_on && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)) return 0;
   return 2;
 }
 
@@ -1761,6 +1795,67 @@ int cc_rig_solver_status(cc_rig* h, int32_t* form, int32_t* reruns, char* note, 
   if (form) *form = cc_rig_solver_form(h);
   if (reruns) *reruns = h->form_reruns;
   if (note && note_capacity > 0) std::snprintf(note, (size_t)note_capacity, "%s", h->form_note.c_str());
+  return CC_OK;
+}
+
+int cc_rig_set_inner_iterations(cc_rig* h, int32_t enable, double tolerance) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_set_inner_iterations: NULL handle");
+  if (h->d.kmode || h->exchange || h->comm)
+    return fail(CC_ERR_STATE, "cc_rig_set_inner_iterations: poses-only handles on one device only (no cc_rigk_*, no exchange)");
+  if (!(tolerance >= 0.0) || !std::isfinite(tolerance)) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_set_inner_iterations: tolerance must be finite and >= 0");
+  CC_HIP(hipSetDevice(h->device));
+  if (enable) {
+    if (int rc = rig_inner_alloc(h)) return rc;
+    CC_HIP(hipStreamSynchronize(h->stream));   // (the zeroed state, before a later status read)
+  }
+  if ((enable != 0) != h->inner_on) rig_drop_graphs(h);   // (the hook's launches are part of a captured round)
+  h->inner_on = enable != 0;
+  h->inner_tol = tolerance;
+  return CC_OK;
+}
+
+int cc_rig_inner_pass(cc_rig* h, double* cost_before, double* cost_after, int32_t mini_iterations[4]) {
+  using namespace cc;
+  if (!h || !h->have_state) return fail(CC_ERR_STATE, "cc_rig_inner_pass: no state set");
+  if (h->d.kmode || h->exchange || h->comm)
+    return fail(CC_ERR_STATE, "cc_rig_inner_pass: poses-only handles on one device only (no cc_rigk_*, no exchange)");
+  CC_HIP(hipSetDevice(h->device));
+  if (int rc = rig_inner_alloc(h)) return rc;
+  double c0 = 0.0, c1 = 0.0;
+  if (cost_before) { if (int rc = cc_rig_eval(h, &c0)) return rc; *cost_before = c0; }
+  LmCtl c;
+  if (int rc = rig_read_ctl(h, &c)) return rc;
+  rig_inner_enqueue_groups(rig_inner_dev(h), h->stream, c.cur & 1);
+  CC_HIP(hipGetLastError());
+  CC_HIP(hipStreamSynchronize(h->stream));
+  if (cost_after) { if (int rc = cc_rig_eval(h, &c1)) return rc; *cost_after = c1; }
+  if (mini_iterations) {
+    std::vector<int32_t> it((size_t)(2 * h->C + 2 * h->F));
+    CC_HIP(hipMemcpy(it.data(), h->d_inner_it, it.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int64_t lo[5] = {0, h->C, 2 * h->C, 2 * h->C + h->F, 2 * h->C + 2 * h->F};
+    for (int k = 0; k < 4; ++k) {
+      int32_t m = 0;
+      for (int64_t i = lo[k]; i < lo[k + 1]; ++i) m = std::max(m, it[(size_t)i]);
+      mini_iterations[k] = m;
+    }
+  }
+  return CC_OK;
+}
+
+int cc_rig_inner_status(cc_rig* h, int32_t* passes, int32_t* useful_passes, int32_t* enabled_at_end, double* cost_removed) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_inner_status: NULL handle");
+  double st[RIG_IN_WORDS] = {};
+  if (h->d_inner) {
+    CC_HIP(hipSetDevice(h->device));
+    CC_HIP(hipStreamSynchronize(h->stream));
+    CC_HIP(hipMemcpy(st, h->d_inner, sizeof(st), hipMemcpyDeviceToHost));
+  }
+  if (passes) *passes = (int32_t)st[RIG_IN_PASSES];
+  if (useful_passes) *useful_passes = (int32_t)st[RIG_IN_USEFUL];
+  if (enabled_at_end) *enabled_at_end = st[RIG_IN_ENABLED] != 0.0 ? 1 : 0;
+  if (cost_removed) *cost_removed = st[RIG_IN_REMOVED];
   return CC_OK;
 }
 
@@ -1861,6 +1956,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
   using namespace cc;
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_comm_init: bad arguments (nranks must be 1..32)");
+  if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
   rig_drop_graphs(h);
@@ -1901,6 +1997,7 @@ int cc_rig_exchange_attach(cc_rig* h, int32_t rank, int32_t nranks, const uint8_
   if (!h || !handles || rank < 0 || nranks < 1 || rank >= nranks || nranks > kP2pMaxRanks)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_attach: bad arguments (nranks must be 1..%d)", kP2pMaxRanks);
   if (!h->mailbox.local) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: call cc_rig_exchange_export first");
+  if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   if (h->comm) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: an RCCL communicator is already attached");
   if (h->C > 128) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_attach: at most 128 cameras with the mailbox exchange");
   CC_HIP(hipSetDevice(h->device));

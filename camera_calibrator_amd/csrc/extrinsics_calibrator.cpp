@@ -120,6 +120,14 @@ void ExtrinsicsCalibrator::Optimize() {
   for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (int64_t)frames_[f].NumObservations();
   const size_t N = (size_t)offsets[F];
   const bool several = devices_.size() > 1;
+  last_inner_passes_ = 0;
+  if (inner_iterations_ && several) {   // inner iterations run on one device only (cc_rig_set_inner_iterations)
+    last_status_ = CC_ERR_STATE;
+    last_iterations_ = 0;
+    return;
+  }
+  // flat copies of the observations: cc_rig_optimize_multi (several devices), the handle API (inner iterations)
+  const bool flat = several || inner_iterations_;
   // frames in contiguous ranges of about equal observation counts, one host thread each (flattening for several devices)
   std::vector<size_t> part_first{0};
   {
@@ -136,8 +144,8 @@ void ExtrinsicsCalibrator::Optimize() {
   uint64_t* obs_world = nullptr;
   float* obs_uv = nullptr;
   double* half_rho = nullptr;
-  if (several) {
-    // several devices: flat copies of the observations for cc_rig_optimize_multi, kept between calls
+  if (flat) {
+    // several devices / inner iterations: flat copies of the observations, kept between calls
     if (flat_.cam.size() < N) {
       // a fresh object (the reference's workflow may build one per call): take over the arrays the last object left behind
       std::lock_guard<std::mutex> lk(g_flat_mu);
@@ -173,8 +181,29 @@ void ExtrinsicsCalibrator::Optimize() {
   summary.log_capacity = (int32_t)log.size();
   const double huber_a = 3.0f / 500.0f;  // extrinsics_calibrator.cpp:176 (float literal, as in the reference)
   last_status_ = 0;
+  bool handle_status = false;   // the solver status came from the handle (inner iterations), not from the one-shot call
   if (N > 0 && C > 0 && F > 0) {
-    if (devices_.size() > 1) {
+    if (inner_iterations_) {
+      // one device with inner iterations: through the handle (create -> set_state -> set_inner_iterations -> solve -> get_state)
+      cc_rig* h = nullptr;
+      last_status_ = cc_rig_create(device_, (int64_t)C, (int64_t)F, (int64_t)Pn, offsets.data(), obs_cam, obs_world, obs_uv, world.data(),
+                                   frozen.data(), huber_a, &h);
+      if (last_status_ == 0) last_status_ = cc_rig_set_state(h, cam_q.data(), cam_t.data(), frame_q.data(), frame_t.data());
+      if (last_status_ == 0) last_status_ = cc_rig_set_inner_iterations(h, 1, 1e-3);   // (Ceres' inner_iteration_tolerance)
+      if (last_status_ == 0) last_status_ = cc_rig_solve(h, &options, &summary);
+      if (last_status_ == 0) last_status_ = cc_rig_get_state(h, cam_q.data(), cam_t.data(), frame_q.data(), frame_t.data(), half_rho);
+      if (last_status_ == 0) cc_rig_inner_status(h, &last_inner_passes_, nullptr, nullptr, nullptr);
+      if (h) {
+        char note[640] = "";
+        int32_t form = 0, reruns = 0;
+        cc_rig_solver_status(h, &form, &reruns, note, (int32_t)sizeof(note));
+        handle_status = true;
+        last_solver_reruns_ = reruns;
+        last_solver_form_ = form;
+        last_solver_note_ = note;
+        cc_rig_destroy(h);
+      }
+    } else if (devices_.size() > 1) {
       std::vector<int32_t> devs(devices_.begin(), devices_.end());
       last_status_ = cc_rig_optimize_multi(&options, (int32_t)devs.size(), devs.data(), (int64_t)C, (int64_t)F, (int64_t)Pn, offsets.data(),
                                            obs_cam, obs_world, obs_uv, world.data(), cam_q.data(), cam_t.data(),
@@ -206,7 +235,7 @@ void ExtrinsicsCalibrator::Optimize() {
   }
   last_iterations_ = summary.iterations;
   last_final_cost_ = summary.final_cost;
-  {
+  if (!handle_status) {
     char note[640] = "";
     int32_t form = 0, reruns = 0;
     cc_last_call_solver_status(&form, &reruns, note, (int32_t)sizeof(note));
@@ -231,7 +260,7 @@ void ExtrinsicsCalibrator::Optimize() {
     over_frames([&](size_t f0, size_t f1) {
       for (size_t f = f0; f < f1; ++f) std::fill(frames_[f].obs_half_rho.begin(), frames_[f].obs_half_rho.end(), 0.0);
     });
-  else if (several && N > 0 && C > 0 && F > 0)
+  else if (flat && N > 0 && C > 0 && F > 0)
     over_frames([&](size_t f0, size_t f1) {
       for (size_t f = f0; f < f1; ++f) {
         if (frames_[f].NumObservations()) std::memcpy(frames_[f].obs_half_rho.data(), half_rho + offsets[f], frames_[f].NumObservations() * sizeof(double));

@@ -46,6 +46,11 @@ class ExtrinsicsCalibrator {
   void SetVerbose(bool verbose) { verbose_ = verbose; }
   int LastStatus() const { return last_status_; }
   int LastIterations() const { return last_iterations_; }
+  /// Ceres' inner iterations (Solver::Options::use_inner_iterations; off by default, parity with Ceres unpinned): one device
+  /// only -- with several (SetDevices) Optimize sets LastStatus() to CC_ERR_STATE and leaves the problem as it was.
+  void SetInnerIterations(bool enable) { inner_iterations_ = enable; }
+  /// Inner passes the last Optimize ran (cc_rig_inner_status); 0 with inner iterations off.
+  int LastInnerPasses() const { return last_inner_passes_; }
   /// Did the last call's solve have to be run AGAIN in another form of the solver (cc_last_call_solver_status: the persistent
   /// one-launch kernel gave up because its workgroups were not resident together -- another tenant on the GPU, a tool that
   /// serialises kernels, another host thread inside a device-wide runtime call)? > 0: that many times; the call was late by 42 ms
@@ -109,6 +114,8 @@ class ExtrinsicsCalibrator {
   bool verbose_{true};
   int last_status_{0};
   int last_iterations_{0};
+  bool inner_iterations_{false};
+  int last_inner_passes_{0};
   int last_solver_reruns_{0};
   int last_solver_form_{0};
   std::string last_solver_note_;

@@ -298,6 +298,23 @@ int cc_rig_solver_form(cc_rig* h);
  * and were run again in form 0; note (NUL-terminated, truncated to note_capacity) = the reason of the last one -- round
  * reached, workers started, whether and where the control workgroup ran. Any output may be NULL. */
 int cc_rig_solver_status(cc_rig* h, int32_t* form, int32_t* reruns, char* note, int32_t note_capacity);
+/* Ceres' inner iterations (Solver::Options::use_inner_iterations, CoordinateDescentMinimizer) for the poses-only rig
+ * problem on one device; off by default. Semantics restated from Ceres 2.x, parity with Ceres unpinned:
+ * after every candidate of a valid step with a finite cost, one inner pass visits the blocks group by group -- every camera's
+ * t_cr, every camera's q_cr, every frame's t_rw, every frame's q_rw -- and minimises each with the others held (a trust-region
+ * LM with Ceres' default Solver::Options, 50 iterations); the pass's cost reduction is added to the model cost change, the step
+ * succeeds when the pass ends below the current cost or the relative decrease passes, and the passes stop for the rest of the
+ * solve once one removes no more than `tolerance` (Ceres' inner_iteration_tolerance, 1e-3) of the candidate's cost.
+ * cc_rig_set_inner_iterations applies to later cc_rig_solve calls; enabled, the handle solves in form 0 (three kernels per
+ * iteration; cc_rig_solver_form reports 0). CC_ERR_STATE for a cc_rigk_* handle and for a handle with an exchange or an
+ * all-reduce attached: those are out of scope (cc_rig_comm_init / cc_rig_exchange_attach refuse a handle with them on).
+ * cc_rig_inner_pass: one pass from the current state, which it updates (a test and measurement aid); costs before and after;
+ * mini_iterations[g] = the most iterations any block of group g (0 t_cr, 1 q_cr, 2 t_rw, 3 q_rw) ran. Outputs may be NULL.
+ * cc_rig_inner_status: the last solve's passes, passes that ended below the current cost, whether the passes were still enabled
+ * at its end, and the cost the passes removed in all. Any output may be NULL. */
+int cc_rig_set_inner_iterations(cc_rig* h, int32_t enable, double tolerance);
+int cc_rig_inner_pass(cc_rig* h, double* cost_before, double* cost_after, int32_t mini_iterations[4]);
+int cc_rig_inner_status(cc_rig* h, int32_t* passes, int32_t* useful_passes, int32_t* enabled_at_end, double* cost_removed);
 /* Any output may be NULL. obs_cost[k] = 1/2 rho(|r_k|^2) at the current point, in the caller's
  * observation order (extrinsics_calibrator.cpp:219-225). */
 int cc_rig_get_state(cc_rig* h, double* cam_q, double* cam_t, double* frame_q, double* frame_t,
