@@ -930,19 +930,9 @@ __global__ __launch_bounds__(256) void k_intr_reset(IntrDev P, const double* ini
 // =============================================================================================
 // host side
 // =============================================================================================
-namespace cc {
+#include "cc_solve_host.hpp"
 
-// RCCL, resolved lazily with dlopen so that single-GPU use never loads it (cc_comm.cpp)
-struct Comm;
-int comm_create(const uint8_t id[128], int rank, int nranks, Comm** out);
-void comm_destroy(Comm* c);
-int comm_allreduce_sum(Comm* c, double* buf, int n, hipStream_t stream);
-
-}  // namespace cc
-
-struct cc_intrinsics {
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct cc_intrinsics : cc::SolveHost {   // pinned: a cached 512-byte block, host_pub (160 B) | h_ctl | h_opts
   cc::IntrDev d{};
   int64_t F = 0, N = 0;
   int elim_blocks = 1;
@@ -955,32 +945,14 @@ struct cc_intrinsics {
   double* init_intr = nullptr;  // [16]
   double* init_pose = nullptr;  // [F][8]
   bool have_state = false;
-  void* pinned = nullptr;      // cached 512-byte pinned block: host_pub (160 B) | h_ctl | h_opts
-  volatile unsigned long long* host_pub = nullptr;  // [0] sequence word written by the device, [2..19] control block
-  unsigned long long pub_count = 0;                 // chunks published so far (what the sequence word will read next: + 1)
-  cc::LmCtl* h_ctl = nullptr;  // pinned
   cc::LmOpts* h_opts = nullptr;  // pinned staging of the options
-  cc::LmOpts cached_opts{};     // what the device currently holds
-  bool opts_valid = false;
   bool ctl_fresh = false;       // the next solve starts from the point of the last set_state
   bool reset_pending = false;   // ... and the device buffers have not been restored yet (lazy: the first round of the
                                 // solve runs as the restart round, cc_intrinsics_reset costs no launch of its own)
-  // [0]: initial evaluation as the restart round + check_interval iterations, [1]: check_interval iterations,
+  // graph[0]: initial evaluation as the restart round + check_interval iterations, [1]: check_interval iterations,
   // [2]: initial evaluation + check_interval iterations (continuing from the accepted point of the last solve)
-  hipGraphExec_t graph[3] = {nullptr, nullptr, nullptr};
-  int graph_iters = 0;
-  cc::Comm* comm = nullptr;
-  // mailbox exchange (cc_intrinsics_exchange_export / _attach): our mailbox and the peers' mappings
-  cc::Mailbox mailbox;
-  bool exchange = false;
-  std::vector<hipEvent_t> events;
-  std::vector<int> event_kind;
-  std::vector<int> event_round;   // round of the solve a probed launch belongs to (summarise_probes)
-  int enq_round = 0;
-  // persistent per-solve kernel (cc_intrinsics_persist.hip): usable when every frame gets a team of a resident workgroup
-  int ran_form = -1;            // the form the handle's LAST solve ran in to its end (-1: none yet): 0 two kernels per iteration, else frames per persistent workgroup
-  int form_reruns = 0;          // persistent solves that gave up and were run again in the two-kernel form (cc_intrinsics_solver_status)
-  std::string form_note;        // why
+  // ran_form: 0 two kernels per iteration, else frames per workgroup of the persistent per-solve kernel
+  // (cc_intrinsics_persist.hip), which is usable when every frame gets a team of a resident workgroup
   bool persist_ok = false;      // ... on a device of its own
   bool persist_x_ok = false;    // ... as one rank of an exchange: every rank fits next to the ranks it shares its device with,
                                 // and every rank said so (cc_intrinsics_exchange_attach / cc_intrinsics_optimize_multi agree on it)
@@ -992,26 +964,11 @@ struct cc_intrinsics {
 
 namespace cc {
 
-static void drop_graphs(cc_intrinsics* h) {
-  for (auto& g : h->graph)
-    if (g) { hipGraphExecDestroy(g); g = nullptr; }
-}
-
 static void exchange_release(cc_intrinsics* h) {
   mailbox_release(&h->mailbox);
   h->d.x = P2pDev{};
   h->exchange = false;
 }
-
-struct Probe {  // optional hipEvent bracket around one launch
-  cc_intrinsics* h; int kind; bool on; int round_shift; hipEvent_t e0 = nullptr, e1 = nullptr;
-  Probe(cc_intrinsics* h_, int kind_, bool on_, int round_shift_ = 0) : h(h_), kind(kind_), on(on_), round_shift(round_shift_) {
-    if (on) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, h->stream); }
-  }
-  ~Probe() {
-    if (on) { hipEventRecord(e1, h->stream); h->events.push_back(e0); h->events.push_back(e1); h->event_kind.push_back(kind); h->event_round.push_back(h->enq_round + round_shift); }
-  }
-};
 
 static void launch_sweep(cc_intrinsics* h, bool profile, int flags = 0) {
   Probe p(h, CC_K_SWEEP, profile);
@@ -1055,12 +1012,6 @@ static int enqueue_round(cc_intrinsics* h, bool profile, bool initial, bool publ
   return 0;
 }
 
-static int write_ctl(cc_intrinsics* h, const LmCtl& c) {
-  CC_HIP(hipMemcpyAsync(h->d.ctl, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-  CC_HIP(hipMemcpyAsync(h->d.ctl_next, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-  return 0;
-}
-
 // restores the point of the last set_state on the device if that is still owed (see reset_pending)
 static int flush_reset(cc_intrinsics* h) {
   if (!h->reset_pending) return 0;
@@ -1078,25 +1029,9 @@ static int read_ctl(cc_intrinsics* h, LmCtl* c) {
   return 0;
 }
 
-// Waits for the chunk just enqueued: spins on the sequence word its last kernel stores into pinned host memory
-// (no copy engine, no stream synchronisation on the way), then takes the control block from next to it. A
-// stream that has gone idle without the word showing up (a kernel fault, a stale counter) falls back to a copy.
-static int wait_published(cc_intrinsics* h, LmCtl* c) {
-  const unsigned long long want = ++h->pub_count;
-  for (unsigned spins = 0;; ++spins) {
-    if (__atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE) == want) break;
-    if ((spins & 0xfffu) == 0xfffu) {
-      const hipError_t q = hipStreamQuery(h->stream);
-      if (q == hipSuccess) {
-        if (__atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE) == want) break;
-        h->pub_count = __atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE);
-        return read_ctl(h, c);
-      }
-      if (q != hipErrorNotReady) return fail(CC_ERR_HIP, "stream failed while waiting for the solver: %s", hipGetErrorString(q));
-    }
-  }
-  std::memcpy(c, const_cast<const unsigned long long*>(h->host_pub) + 2, sizeof(LmCtl));
-  return 0;
+// the chunk just enqueued has published its control block (wait_published, cc_solve_host.hpp; no failure word, one stream)
+static int wait_chunk(cc_intrinsics* h, LmCtl* c) {
+  return wait_published(h, nullptr, c, nullptr, "the solver", [=] { return read_ctl(h, c); });
 }
 
 }  // namespace cc
@@ -1147,11 +1082,8 @@ int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const fl
 
 int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]) {
   using namespace cc;
-  if (!h || !handle) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_exchange_export: NULL argument");
-  CC_HIP(hipSetDevice(h->device));
-  CC_HIP(hipStreamSynchronize(h->stream));
-  drop_graphs(h);
-  exchange_release(h);
+  if (int rc = exchange_export_begin(h, handle, "cc_intrinsics_exchange_export")) return rc;
+  h->d.x = P2pDev{};
   return mailbox_export(&h->mailbox, kVecSolve, 16, handle);
 }
 
@@ -1468,49 +1400,26 @@ int cc_intrinsics_eval(cc_intrinsics* h, double* blocks, double* cost) {
 }  // extern "C"
 
 namespace cc {
-// Captures `rounds` rounds (the first one optionally as the restart round) into an executable graph. On any failure the
-// stream is taken out of capture mode again and nothing is kept (a stream left capturing would poison the
-// process-wide stream cache it returns to).
+// Captures `rounds` rounds (the first one optionally as the restart round) into an executable graph.
 static int capture_chunk(cc_intrinsics* h, bool with_reset, bool initial, int rounds, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  CC_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int i = 0; i < rounds && !rc; ++i) rc = enqueue_round(h, false, initial && i == 0, i == rounds - 1, with_reset && i == 0);
-  const hipError_t e_end = hipStreamEndCapture(h->stream, &g);
-  if (rc || e_end != hipSuccess) {
-    if (g) hipGraphDestroy(g);
-    (void)hipGetLastError();
-    return rc ? rc : fail(CC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e_end));
-  }
-  const hipError_t e_inst = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e_inst != hipSuccess) { *out = nullptr; return fail(CC_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e_inst)); }
-  return 0;
+  return capture_graph(h, out, [=] {
+    int rc = 0;
+    for (int i = 0; i < rounds && !rc; ++i) rc = enqueue_round(h, false, initial && i == 0, i == rounds - 1, with_reset && i == 0);
+    return rc;
+  });
 }
 }  // namespace cc
 
 namespace cc {
 // A solve in phases, so that ONE host thread can drive several handles (devices) in lock step:
 // begin (state, options) -> { launch a chunk on every handle -> wait for every handle } ... -> finish.
-struct SolveRun {
-  cc_options o;
-  bool profile = false, use_graph = false, host_word = false;
-  int launched = 0;
-  LmCtl st{};
-  std::chrono::steady_clock::time_point t0;
+struct SolveRun : SolveRunBase {
+  bool host_word = false;
 };
 
 static int solve_begin(cc_intrinsics* h, const cc_options* opt, SolveRun* r) {
-  r->t0 = std::chrono::steady_clock::now();
-  if (opt) r->o = *opt; else cc_options_init(&r->o);
-  cc_options& o = r->o;
-  if (o.check_interval < 1) o.check_interval = 1;
-  if (o.max_iterations > h->d.log_cap - 1) o.max_iterations = h->d.log_cap - 1;
-  r->profile = o.profile_kernels != 0;
-  r->use_graph = o.use_graph && !r->profile && !h->comm;
+  if (int rc = begin_common(h, opt, h->d.log_cap, r)) return rc;
   r->host_word = !h->comm;   // fused routes hand the control block over through pinned memory
-  r->launched = 0;
-  CC_HIP(hipSetDevice(h->device));
   if (!h->ctl_fresh) {
     // continue from the accepted point of the previous run: move it to buffer 0, fresh control block
     LmCtl st;
@@ -1525,20 +1434,13 @@ static int solve_begin(cc_intrinsics* h, const cc_options* opt, SolveRun* r) {
   }
   h->ctl_fresh = false;
   LmOpts lo;
-  opts_from_public(o, &lo);
-  if (!h->opts_valid || std::memcmp(&lo, &h->cached_opts, sizeof(lo)) != 0) {
+  opts_from_public(r->o, &lo);
+  if (opts_changed(h, lo)) {
     CC_HIP(hipStreamSynchronize(h->stream));  // the pinned staging buffer may still be in flight
     *h->h_opts = lo;
     CC_HIP(hipMemcpyAsync(h->d.opts, h->h_opts, sizeof(lo), hipMemcpyHostToDevice, h->stream));
-    h->cached_opts = lo;
     h->opts_valid = true;
   }
-  for (auto e : h->events) hipEventDestroy(e);
-  h->events.clear();
-  h->event_kind.clear();
-  h->event_round.clear();
-  h->enq_round = 0;
-  if (r->use_graph && h->graph_iters != o.check_interval) { drop_graphs(h); h->graph_iters = o.check_interval; }
   return 0;
 }
 
@@ -1569,7 +1471,7 @@ static int solve_launch(cc_intrinsics* h, SolveRun* r, int chunk) {
 
 static int solve_wait(cc_intrinsics* h, SolveRun* r) {
   CC_HIP(hipSetDevice(h->device));
-  if (int rc = r->host_word ? wait_published(h, &r->st) : read_ctl(h, &r->st)) return rc;
+  if (int rc = r->host_word ? wait_chunk(h, &r->st) : read_ctl(h, &r->st)) return rc;
   if (r->st.done && r->st.term == CC_FAILURE_EXCHANGE) {
     (void)hipStreamSynchronize(h->stream);
     const std::string where = h->exchange ? mailbox_describe(&h->mailbox, h->d.rank, h->d.nranks) : std::string();
@@ -1612,7 +1514,7 @@ static int persistent_launch(cc_intrinsics* h, SolveRun* r) {
 
 static int persistent_wait(cc_intrinsics* h, SolveRun* r) {
   CC_HIP(hipSetDevice(h->device));
-  if (int rc = wait_published(h, &r->st)) return rc;
+  if (int rc = wait_chunk(h, &r->st)) return rc;
   if (r->st.done && r->st.term == CC_FAILURE_EXCHANGE) {
     CC_HIP(hipMemsetAsync(h->pq.fail, 0, sizeof(unsigned), h->stream));
     (void)hipStreamSynchronize(h->stream);
@@ -1645,31 +1547,6 @@ static int solve_persistent(cc_intrinsics* h, SolveRun* r) {
   return persistent_wait(h, r);
 }
 
-static int solve_finish(cc_intrinsics* h, SolveRun* r, cc_summary* summary) {
-  const LmCtl& st = r->st;
-  CC_HIP(hipSetDevice(h->device));
-  if (summary) {
-    cc_iteration* user_log = summary->log;
-    const int cap = summary->log_capacity;
-    summary->iterations = st.iter;
-    summary->successful_steps = st.n_success;
-    summary->termination = st.term;
-    summary->initial_cost = st.initial_cost;
-    summary->final_cost = st.x_cost;
-    summary->sweeps = st.sweeps;
-    const int n = user_log ? std::min(std::min(st.log_len, cap), h->d.log_cap) : 0;
-    summary->log_len = n;
-    if (n > 0) CC_HIP(hipMemcpy(user_log, h->d.log, (size_t)n * sizeof(cc_iteration), hipMemcpyDeviceToHost));
-    summarise_probes(h->events, r->profile ? h->event_kind : std::vector<int>(), h->event_round, st.iter, summary,
-                     [](float* ms, hipEvent_t a, hipEvent_t b) { return hipEventElapsedTime(ms, a, b) == hipSuccess; });
-    summary->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - r->t0).count();
-  }
-  for (auto e : h->events) hipEventDestroy(e);
-  h->events.clear();
-  h->event_kind.clear();
-  h->event_round.clear();
-  return CC_OK;
-}
 }  // namespace cc
 
 extern "C" {
@@ -1687,9 +1564,10 @@ int cc_intrinsics_solve(cc_intrinsics* h, const cc_options* opt, cc_summary* sum
   if (use_persistent(h, &r) && (!alone || persist_device_try(h->device, 0))) {
     // ONE launch runs the whole solve (cc_intrinsics_persist.hip); the host waits for its publication
     const bool was_restart = h->reset_pending;
+    PersistProbe probe(h->device, 0, alone);
     const int rc = solve_persistent(h, &r);
-    if (alone) { if (rc == CC_OK) persist_device_completed(h->device, 0); else persist_device_gave_up(h->device, 0); }
-    if (rc == CC_OK) { h->ran_form = h->pq.teams; return solve_finish(h, &r, summary); }
+    if (rc == CC_OK) { probe.completed(); h->ran_form = h->pq.teams; return finish_summary(h, &r, summary); }
+    probe.gave_up();
     if (rc != CC_ERR_COMM || h->exchange) return rc;
     // A wait inside the kernel gave up after 1.3 s: its workgroups were not all resident (another process on the device,
     // a compute-unit mask). Nothing was written back, so the solve is run again -- and this handle keeps to -- the
@@ -1715,7 +1593,7 @@ int cc_intrinsics_solve(cc_intrinsics* h, const cc_options* opt, cc_summary* sum
     if (r.st.done) break;
   }
   h->ran_form = 0;
-  return solve_finish(h, &r, summary);
+  return finish_summary(h, &r, summary);
 }
 
 // Multi-device solve driven by ONE host thread (SURVEY.md 8(b) thread model): the frames are split into contiguous
@@ -1787,7 +1665,7 @@ int cc_intrinsics_optimize_multi(const cc_options* opt, int32_t n_devices, const
     if (all_done) break;
     if (any_done) rc = fail(CC_ERR_STATE, "cc_intrinsics_optimize_multi: the shards disagree about termination");
   }
-  if (!rc) rc = solve_finish(hs[0], &runs[0], summary);
+  if (!rc) rc = finish_summary(hs[0], &runs[0], summary);
   for (int r = 0; r < n && !rc; ++r) {
     const int64_t f0 = first[(size_t)r];
     rc = cc_intrinsics_get_state(hs[(size_t)r], r == 0 ? intr9 : nullptr, q + 4 * f0, t + 3 * f0);
@@ -1822,10 +1700,7 @@ int cc_intrinsics_solver_form(cc_intrinsics* h) {
 int cc_intrinsics_solver_status(cc_intrinsics* h, int32_t* form, int32_t* reruns, char* note, int32_t note_capacity) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_solver_status: NULL handle");
-  if (form) *form = cc_intrinsics_solver_form(h);
-  if (reruns) *reruns = h->form_reruns;
-  if (note && note_capacity > 0) std::snprintf(note, (size_t)note_capacity, "%s", h->form_note.c_str());
-  return CC_OK;
+  return solver_status(h, cc_intrinsics_solver_form(h), form, reruns, note, note_capacity);
 }
 
 int cc_intrinsics_profile_solve(cc_intrinsics* h, const cc_options* opt, int32_t n, double* avg_launch_ms, int32_t* sweeps_per_launch) {

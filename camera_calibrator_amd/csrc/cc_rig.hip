@@ -293,21 +293,14 @@ __global__ void k_rig_obs_cost(RigDev P, int cur, double* out /*sorted order*/) 
 // =============================================================================================
 // host side
 // =============================================================================================
-namespace cc {
-struct Comm;
-int comm_create(const uint8_t id[128], int rank, int nranks, Comm** out);
-void comm_destroy(Comm* c);
-int comm_allreduce_sum(Comm* c, double* buf, int n, hipStream_t stream);
-}  // namespace cc
+#include "cc_solve_host.hpp"
 
 // dynamic LDS of the persistent kernels' control workgroup: the solve step's, the reduced row, the destination tables
 static size_t rig_persist_ctl_lds(size_t solve_lds, const cc::RigDev& d) {
   return solve_lds + (size_t)(d.PC + 32) * 8 + (((size_t)4 * (d.nT * 256 + 2 * d.ND) + (size_t)4 * d.ND + 7) & ~(size_t)7);
 }
 
-struct cc_rig {
-  int device = 0;
-  hipStream_t stream = nullptr;
+struct cc_rig : cc::SolveHost {   // pinned: host_pub = h_ctl's block, [20] failure word, [22] the lean form's residency gate
   cc::RigDev d{};
   int64_t C = 0, F = 0, N = 0, NG = 0, P = 0;
   int n_runs = 0;            // runs of shared columns (one per optimised camera, one per intrinsics set): blocks of k_rig_init
@@ -329,16 +322,10 @@ struct cc_rig {
   double* init_pose = nullptr;
   double* d_cost = nullptr;
   bool have_state = false;
-  cc::LmCtl* h_ctl = nullptr;
-  void* pinned = nullptr;       // the pinned block h_ctl and host_pub live in
-  hipGraphExec_t graph[3] = {nullptr, nullptr, nullptr};   // first chunk (with the preparation) | chunk of check_interval rounds | of twice as many
-  int graph_iters = 0;
-  cc::Comm* comm = nullptr;
-  cc::Mailbox mailbox;          // mailbox exchange (cc_rig_exchange_export / _attach)
+  // graph[]: first chunk (with the preparation) | chunk of check_interval rounds | of twice as many
   double* init_intr = nullptr;  // [max(CK,1)][16] (extension)
   uint32_t* d_kmask = nullptr;  // same memory as d.kmask
   bool have_intr = false;
-  bool exchange = false;
   uint8_t* d_cam_fixed = nullptr;          // same memory as d.cam_fixed
   std::vector<uint8_t> frozen, seen;       // host copies (user freeze flags, locally observed cameras)
   std::vector<uint8_t> seen_any;           // cameras observed by any rank (what the column layout is built for)
@@ -352,10 +339,8 @@ struct cc_rig {
   double* d_cam_backup = nullptr;   // [C][8] cameras of the starting point (the lean persistent solve may be run again in the three-kernel form)
   int p_teams = 4;              // frames per workgroup of the lean form
   bool persist_w_ok = false;    // ... and so can its lean form (k_rig_persist_w + k_rig_persist_ctl: <= 4 observed cameras, <= 24 shared coordinates)
-  int ran_form = -1;               // the form the handle's LAST solve ran in to its end (-1: none yet): 0 three kernels per iteration, 2 the lean persistent pair
-  int form_reruns = 0;             // lean persistent solves that gave up and were run again in the three-kernel form
-  int lean_strikes = 0;            // ... of them in the first round, in a row (two demote the handle)
-  std::string form_note;           // why (cc_rig_solver_status)
+  // (ran_form: 0 three kernels per iteration, 2 the lean persistent pair)
+  int lean_strikes = 0;            // lean solves that gave up in the first round, in a row (two demote the handle)
   hipStream_t stream2 = nullptr;   // the control workgroup's launch of the lean form
   hipEvent_t ev_begin = nullptr;
   cc::RigPersistDev pq{};
@@ -363,20 +348,12 @@ struct cc_rig {
   size_t p_box_words = 0;       // seam boxes: one allocation of this many 8-byte words (re-zeroed before the tags wrap)
   bool big_packed = false;      // ... with the reduced system as a packed triangle in LDS (else in bigA, global memory)
   double* bigA = nullptr;
-  volatile unsigned long long* host_pub = nullptr;   // = h_ctl's pinned block: [0] sequence word, [2..19] control block, [20] failure word
-  unsigned long long pub_count = 0;                  // chunks published so far
   cc::LmCtl last_st{};          // control block as the last solve / reset left it (no read-back at the start of a solve)
   bool st_known = false;
-  cc::LmOpts cached_opts{};     // what the device holds
-  bool opts_valid = false;
   int co_resident = 1;         // shards / processes whose k_rig_reduce launches share this device (cc_rig_optimize_multi counts them,
                                // cc_rig_exchange_attach derives ceil(ranks / visible devices); CC_RIG_CO_RESIDENT overrides)
   int reduce_blocks = 0;       // grid of the fused reduce + solve + update launch (rig_size_reduce_grid)
   size_t reduce_key = ~(size_t)0;
-  std::vector<hipEvent_t> events;
-  std::vector<int> event_kind;
-  std::vector<int> event_round;   // round of the solve a probed launch belongs to (summarise_probes)
-  int enq_round = 0;
   // inner iterations (cc_rig_set_inner_iterations; cc_rig_inner.hpp)
   bool inner_on = false;
   double inner_tol = 1e-3;
@@ -429,21 +406,6 @@ static int dev_upload(cc_rig* h, const T** p, const std::vector<T>& v) {
   *p = q;
   return 0;
 }
-
-static void rig_drop_graphs(cc_rig* h) {
-  for (auto& g : h->graph)
-    if (g) { hipGraphExecDestroy(g); g = nullptr; }
-}
-
-struct RigProbe {  // optional hipEvent bracket around one launch
-  cc_rig* h; int kind; bool on; int round_shift; hipEvent_t e0 = nullptr, e1 = nullptr;
-  RigProbe(cc_rig* h_, int kind_, bool on_, int round_shift_ = 0) : h(h_), kind(kind_), on(on_), round_shift(round_shift_) {
-    if (on) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, h->stream); }
-  }
-  ~RigProbe() {
-    if (on) { hipEventRecord(e1, h->stream); h->events.push_back(e0); h->events.push_back(e1); h->event_kind.push_back(kind); h->event_round.push_back(h->enq_round + round_shift); }
-  }
-};
 
 // hipFuncAttributeMaxDynamicSharedMemorySize, set once per (device, kernel) and size: a handle's layout asks for ~20 of them, a
 // fresh handle per call (the reference's workflow) would pay ~10 us each every time
@@ -653,7 +615,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim_big<true>), (int)h->elim_lds)) return rc_;
     if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_solve_big<true>), (int)h->solve_lds)) return rc_;
     if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_solve_big<false>), (int)h->solve_lds)) return rc_;
-    rig_drop_graphs(h);
+    drop_graphs(h);
     return 0;
   }
   if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<false, 8>), (int)h->elim_lds)) return rc_;
@@ -742,7 +704,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
       if (!pays && !h->persist_lean_forced) h->persist_w_ok = false;
     }
   }
-  rig_drop_graphs(h);
+  drop_graphs(h);
   return 0;
 }
 
@@ -792,7 +754,7 @@ static int rig_size_reduce_grid(cc_rig* h) {
   if (key == h->reduce_key && h->reduce_blocks > 0) return 0;
   if (h->big || rig_unfused_exchange(h)) {   // column sums only (k_rig_reduce<2> / <4>): nothing waits inside that launch
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(rcap, (h->d.PC + 15) / 16));
-    if (blocks != h->reduce_blocks) rig_drop_graphs(h);
+    if (blocks != h->reduce_blocks) drop_graphs(h);
     h->reduce_blocks = blocks;
     h->reduce_key = key;
     return 0;
@@ -810,7 +772,7 @@ static int rig_size_reduce_grid(cc_rig* h) {
   const int64_t resident = std::max<int64_t>(1, (int64_t)per_cu * cus * 7 / 8 / co);
   const int64_t want = std::max<int64_t>((h->d.PC + 15) / 16, (h->F + 15) / 16);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(rcap, want), resident));
-  if (blocks != h->reduce_blocks) rig_drop_graphs(h);   // the grid is baked into captured launches
+  if (blocks != h->reduce_blocks) drop_graphs(h);   // the grid is baked into captured launches
   h->reduce_blocks = blocks;
   h->reduce_key = key;
   return 0;
@@ -853,7 +815,7 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     else if (h->sweep_waves == 2) hipLaunchKernelGGL((k_rig_sweep_adj<2>), dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);
     else hipLaunchKernelGGL((k_rig_sweep_adj<1>), dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
   };
-  { RigProbe p(h, CC_K_SWEEP, profile); sweep(); }
+  { Probe p(h, CC_K_SWEEP, profile); sweep(); }
   if (h->inner_on && !initial && !h->comm && !h->exchange) {
     // inner iterations (cc_rig_inner.hpp): a pass on the candidate, the sweep again at its result, the decision with the
     // augmented model. Every launch returns at once in a round without a pass; none is probed (kept out of kernel_ms).
@@ -863,28 +825,28 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     rig_inner_enqueue_decide(I, h->stream);
   }
   if (h->comm || h->exchange) {
-    { RigProbe p(h, CC_K_DECIDE, profile); hipLaunchKernelGGL(k_rig_stats, dim3(1), dim3(256), 0, h->stream, d); }
-    if (h->comm) { RigProbe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec_stats, 4 + d.S, h->stream)) return rc; }
+    { Probe p(h, CC_K_DECIDE, profile); hipLaunchKernelGGL(k_rig_stats, dim3(1), dim3(256), 0, h->stream, d); }
+    if (h->comm) { Probe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec_stats, 4 + d.S, h->stream)) return rc; }
   }
-  if (initial) { RigProbe p(h, CC_K_DECIDE, profile); hipLaunchKernelGGL(k_rig_init, dim3(1 + (unsigned)h->n_runs + (unsigned)h->n_shared_runs * (unsigned)(d.init_slices - 1)), dim3(256), 0, h->stream, d); }
+  if (initial) { Probe p(h, CC_K_DECIDE, profile); hipLaunchKernelGGL(k_rig_init, dim3(1 + (unsigned)h->n_runs + (unsigned)h->n_shared_runs * (unsigned)(d.init_slices - 1)), dim3(256), 0, h->stream, d); }
   if (h->big) {
-    { RigProbe p(h, CC_K_ELIM, profile);
+    { Probe p(h, CC_K_ELIM, profile);
       if (d.kmode) hipLaunchKernelGGL(k_rig_elim_big<true>, dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
       else hipLaunchKernelGGL(k_rig_elim_big<false>, dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d); }
     if (h->exchange) {   // sharded over the mailboxes: posts, then one collecting block (nothing waits inside a launch of many blocks)
-      { RigProbe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<4>, dim3((unsigned)std::max(1, h->reduce_blocks)), dim3(256), 0, h->stream, d, 0); }
-      { RigProbe p(h, CC_K_ALLREDUCE, profile); hipLaunchKernelGGL(k_rig_collect, dim3(1), dim3(256), 0, h->stream, d); }
+      { Probe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<4>, dim3((unsigned)std::max(1, h->reduce_blocks)), dim3(256), 0, h->stream, d, 0); }
+      { Probe p(h, CC_K_ALLREDUCE, profile); hipLaunchKernelGGL(k_rig_collect, dim3(1), dim3(256), 0, h->stream, d); }
     } else {
-      { RigProbe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<2>, dim3((unsigned)std::max(1, h->reduce_blocks)), dim3(256), 0, h->stream, d, 0); }
-      if (h->comm) { RigProbe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec, d.PC + 32, h->stream)) return rc; }
+      { Probe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<2>, dim3((unsigned)std::max(1, h->reduce_blocks)), dim3(256), 0, h->stream, d, 0); }
+      if (h->comm) { Probe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec, d.PC + 32, h->stream)) return rc; }
     }
-    { RigProbe p(h, CC_K_SOLVE, profile);
+    { Probe p(h, CC_K_SOLVE, profile);
       if (h->big_packed) hipLaunchKernelGGL(k_rig_solve_big<true>, dim3(1), dim3(256), h->solve_lds, h->stream, d, h->bigA);
       else hipLaunchKernelGGL(k_rig_solve_big<false>, dim3(1), dim3(256), h->solve_lds, h->stream, d, h->bigA); }
-    { RigProbe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
+    { Probe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
     return 0;
   }
-  { RigProbe p(h, CC_K_ELIM, profile);
+  { Probe p(h, CC_K_ELIM, profile);
     const bool small = d.ND <= 8 * 64;
     if (d.kcm && small) hipLaunchKernelGGL((k_rig_elim<true, 8, false, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
     else if (d.kcm) hipLaunchKernelGGL((k_rig_elim<true, kRigDirectPerLane, false, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
@@ -897,16 +859,16 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
   // (every block of the fused launch must be resident at once: its grid comes from rig_size_reduce_grid, rig_begin)
   const unsigned rblocks = (unsigned)std::max(1, h->reduce_blocks);
   if (h->comm) {
-    { RigProbe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<2>, dim3(rblocks), dim3(256), 0, h->stream, d, 0); }
-    { RigProbe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec, d.PC + 32, h->stream)) return rc; }
-    { RigProbe p(h, CC_K_SOLVE, profile); hipLaunchKernelGGL(k_rig_solve<0>, dim3(1), dim3(256), h->solve_lds, h->stream, d, 0); }
-    { RigProbe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
+    { Probe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<2>, dim3(rblocks), dim3(256), 0, h->stream, d, 0); }
+    { Probe p(h, CC_K_ALLREDUCE, profile); if (int rc = comm_allreduce_sum(h->comm, d.vec, d.PC + 32, h->stream)) return rc; }
+    { Probe p(h, CC_K_SOLVE, profile); hipLaunchKernelGGL(k_rig_solve<0>, dim3(1), dim3(256), h->solve_lds, h->stream, d, 0); }
+    { Probe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
   } else if (rig_unfused_exchange(h)) {   // shared device: nobody waits for a block of its own launch (see rig_unfused_exchange)
-    { RigProbe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<4>, dim3(rblocks), dim3(256), 0, h->stream, d, 0); }
-    { RigProbe p(h, CC_K_SOLVE, profile); hipLaunchKernelGGL(k_rig_solve<2>, dim3(1), dim3(256), h->solve_lds, h->stream, d, publish ? 1 : 0); }
-    { RigProbe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
+    { Probe p(h, CC_K_REDUCE, profile); hipLaunchKernelGGL(k_rig_reduce<4>, dim3(rblocks), dim3(256), 0, h->stream, d, 0); }
+    { Probe p(h, CC_K_SOLVE, profile); hipLaunchKernelGGL(k_rig_solve<2>, dim3(1), dim3(256), h->solve_lds, h->stream, d, publish ? 1 : 0); }
+    { Probe p(h, CC_K_UPDATE, profile); hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, d); }
   } else {   // reduce + solve step + pose update in one launch
-    RigProbe p(h, CC_K_SOLVE, profile);
+    Probe p(h, CC_K_SOLVE, profile);
     if (h->exchange) hipLaunchKernelGGL(k_rig_reduce<3>, dim3(rblocks), dim3(256), h->solve_lds, h->stream, d, publish ? 1 : 0);
     else hipLaunchKernelGGL(k_rig_reduce<0>, dim3(rblocks), dim3(256), h->solve_lds, h->stream, d, publish ? 1 : 0);
   }
@@ -919,45 +881,12 @@ static void rig_enqueue_prep(cc_rig* h) {
   hipLaunchKernelGGL(k_rig_update, dim3((unsigned)((h->F + 15) / 16)), dim3(256), 0, h->stream, h->d);
 }
 
-static int rig_write_ctl(cc_rig* h, const LmCtl& c) {
-  CC_HIP(hipMemcpyAsync(h->d.ctl, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-  CC_HIP(hipMemcpyAsync(h->d.ctl_next, &c, sizeof(c), hipMemcpyHostToDevice, h->stream));
-  return 0;
-}
 // control block as the last kernel left it; *wait_failed (optional): the failure word of k_rig_reduce's in-kernel waits
 static int rig_read_ctl(cc_rig* h, LmCtl* c, bool* wait_failed = nullptr) {
   CC_HIP(hipMemcpyAsync(h->h_ctl, h->d.ctl_next, sizeof(LmCtl) + 4 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
   CC_HIP(hipStreamSynchronize(h->stream));
   *c = *h->h_ctl;
   if (wait_failed) *wait_failed = reinterpret_cast<const unsigned*>(h->h_ctl + 1)[3] != 0u;
-  return 0;
-}
-
-// Waits for the chunk just enqueued: spins on the sequence word its last reduce launch stores into pinned host memory
-// (no copy engine, no stream synchronisation on the way), then takes the control block and the failure word from next
-// to it. A stream that has gone idle without the word showing up (a kernel fault) falls back to a copy.
-// `lean`: the chunk is a lean persistent solve -- its ONLY publisher is the control workgroup on h->stream2, and the workers
-// on h->stream leave as soon as they have seen `done` in their boxes, a few microseconds BEFORE the control has written the
-// control block and the sequence word. The fallback is therefore taken only when BOTH streams are idle (ADVICE round 3:
-// with h->stream alone the host could re-synchronise its count and read a half-written control block while the control
-// workgroup was still publishing, and the late publication then satisfied the NEXT solve's wait at once).
-static int rig_wait_published(cc_rig* h, LmCtl* c, bool* wait_failed, bool lean = false) {
-  const unsigned long long want = ++h->pub_count;
-  for (unsigned spins = 0;; ++spins) {
-    if (__atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE) == want) break;
-    if ((spins & 0xfffu) == 0xfffu) {
-      hipError_t q = hipStreamQuery(h->stream);
-      if (q == hipSuccess && lean && h->stream2) q = hipStreamQuery(h->stream2);
-      if (q == hipSuccess) {
-        if (__atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE) == want) break;
-        h->pub_count = __atomic_load_n(const_cast<const unsigned long long*>(h->host_pub), __ATOMIC_ACQUIRE);
-        return rig_read_ctl(h, c, wait_failed);
-      }
-      if (q != hipErrorNotReady) return fail(CC_ERR_HIP, "stream failed while waiting for the rig solver: %s", hipGetErrorString(q));
-    }
-  }
-  std::memcpy(c, const_cast<const unsigned long long*>(h->host_pub) + 2, sizeof(LmCtl));
-  *wait_failed = h->host_pub[2 + sizeof(LmCtl) / 8] != 0ull;
   return 0;
 }
 
@@ -1413,7 +1342,7 @@ void cc_rig_destroy(cc_rig* h) {
 
   hp.mark("sync");
   if (h->ev_begin) hipEventDestroy(h->ev_begin);
-  cc::rig_drop_graphs(h);
+  cc::drop_graphs(h);
   for (auto e : h->events) hipEventDestroy(e);
   if (h->comm) cc::comm_destroy(h->comm);
   cc::mailbox_release(&h->mailbox);
@@ -1455,7 +1384,7 @@ int cc_rig_reset(cc_rig* h) {
   if (!h || !h->have_state) return fail(CC_ERR_STATE, "cc_rig_reset: no state set");
   CC_HIP(hipSetDevice(h->device));
   LmCtl c{};
-  if (int rc = rig_write_ctl(h, c)) return rc;
+  if (int rc = write_ctl(h, c)) return rc;
   h->last_st = c;
   h->st_known = true;
   CC_HIP(hipMemcpyAsync(h->d.cam, h->init_cam, (size_t)h->C * 8 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -1467,51 +1396,35 @@ int cc_rig_reset(cc_rig* h) {
 }  // extern "C"
 
 namespace cc {
-// Captures the head of a solve (optional) and `rounds` rounds into an executable graph; on any failure the
-// stream is taken out of capture mode again and nothing is kept.
+// Captures the head of a solve (optional) and `rounds` rounds into an executable graph.
 static int rig_capture(cc_rig* h, bool first_chunk, int rounds, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  CC_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  if (first_chunk) rig_enqueue_prep(h);
-  for (int i = 0; i < rounds && !rc; ++i) rc = rig_enqueue_round(h, first_chunk && i == 0, false, i == rounds - 1);
-  const hipError_t e_end = hipStreamEndCapture(h->stream, &g);
-  if (rc || e_end != hipSuccess) {
-    if (g) hipGraphDestroy(g);
-    (void)hipGetLastError();
-    return rc ? rc : fail(CC_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e_end));
-  }
-  const hipError_t e_inst = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  hipGraphDestroy(g);
-  if (e_inst != hipSuccess) { *out = nullptr; return fail(CC_ERR_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(e_inst)); }
-  return 0;
+  return capture_graph(h, out, [=] {
+    int rc = 0;
+    if (first_chunk) rig_enqueue_prep(h);
+    for (int i = 0; i < rounds && !rc; ++i) rc = rig_enqueue_round(h, first_chunk && i == 0, false, i == rounds - 1);
+    return rc;
+  });
 }
 }  // namespace cc
 
 namespace cc {
 // A solve in phases (cf. cc_intrinsics.hip): begin -> { launch a chunk -> wait } ... -> finish, so that one host
 // thread can drive several handles (devices) in lock step.
-struct RigRun {
-  cc_options o;
-  bool profile = false, use_graph = false;
+struct RigRun : SolveRunBase {
   bool persist = false;   // this solve runs as ONE launch of k_rig_persist / k_rig_persist_w
   bool no_persist = false;   // (a rerun after that launch could not get its workgroups resident)
   bool rerun = false;        // set by rig_wait: the lean persistent launch gave up, nothing was written back
-  int launched = 0;
-  LmCtl st{};
-  std::chrono::steady_clock::time_point t0;
 };
 
+// this solve may run in the lean persistent form (k_rig_persist_w + k_rig_persist_ctl)
+static bool rig_lean_eligible(const cc_rig* h, bool profile) {
+  return h->persist_w_ok && !h->inner_on && !profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1;
+}
+
 static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
-  r->t0 = std::chrono::steady_clock::now();
-  if (opt) r->o = *opt; else { cc_options_init(&r->o); r->o.max_iterations = 1000; }  // extrinsics_calibrator.cpp:211
-  cc_options& o = r->o;
-  if (o.check_interval < 1) o.check_interval = 1;
-  if (o.max_iterations > h->d.log_cap - 1) o.max_iterations = h->d.log_cap - 1;
-  r->profile = o.profile_kernels != 0;
-  r->use_graph = o.use_graph != 0 && !h->comm && !r->profile;
-  r->launched = 0;
-  CC_HIP(hipSetDevice(h->device));
+  cc_options dflt;
+  if (!opt) { cc_options_init(&dflt); dflt.max_iterations = 1000; opt = &dflt; }  // extrinsics_calibrator.cpp:211
+  if (int rc = begin_common(h, opt, h->d.log_cap, r)) return rc;
   // (the control block a solve starts from is the one the last solve published or the zeros of a reset: the host has it)
   LmCtl st = h->last_st;
   if (!h->st_known)
@@ -1523,10 +1436,9 @@ static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
     if (h->d.kmode) CC_HIP(hipMemcpyAsync(h->d.intr, h->d.intr + (size_t)h->d.CK * 16, (size_t)h->d.CK * 16 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   }
   LmOpts lo;
-  opts_from_public(o, &lo);
-  if (!h->opts_valid || std::memcmp(&lo, &h->cached_opts, sizeof(lo)) != 0) {   // (uploaded when they change, not per solve)
+  opts_from_public(r->o, &lo);
+  if (opts_changed(h, lo)) {
     CC_HIP(hipMemcpyAsync(h->d.opts, &lo, sizeof(lo), hipMemcpyHostToDevice, h->stream));
-    h->cached_opts = lo;
     h->opts_valid = true;
   }
   if (int rc = rig_size_reduce_grid(h)) return rc;
@@ -1540,18 +1452,12 @@ static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
     h->inner_init[RIG_IN_TOL] = h->inner_tol;
     CC_HIP(hipMemcpyAsync(h->d_inner, h->inner_init, sizeof(h->inner_init), hipMemcpyHostToDevice, h->stream));
   }
-  for (auto e : h->events) hipEventDestroy(e);
-  h->events.clear();
-  h->event_kind.clear();
-  h->event_round.clear();
-  h->enq_round = 0;
-  if (r->use_graph && h->graph_iters != o.check_interval) { rig_drop_graphs(h); h->graph_iters = o.check_interval; }
   return 0;
 }
 
 static int rig_launch(cc_rig* h, RigRun* r, int chunk) {
   CC_HIP(hipSetDevice(h->device));
-  if (chunk == 0 && !r->no_persist && h->persist_w_ok && !h->inner_on && !r->profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1) {
+  if (chunk == 0 && !r->no_persist && rig_lean_eligible(h, r->profile)) {
     // the whole solve in one launch (k_rig_persist); the control workgroup publishes when it is over
     RigPersistDev q = h->pq;
     q.max_rounds = r->o.max_iterations + 2;
@@ -1610,7 +1516,7 @@ static int rig_launch(cc_rig* h, RigRun* r, int chunk) {
   if (r->use_graph) {
     const int which = chunk == 0 ? 0 : (chunk >= 2 ? 2 : 1);
     if (!h->graph[which])
-      if (int rc = rig_capture(h, which == 0, n, &h->graph[which])) { rig_drop_graphs(h); return rc; }
+      if (int rc = rig_capture(h, which == 0, n, &h->graph[which])) { drop_graphs(h); return rc; }
     CC_HIP(hipGraphLaunch(h->graph[which], h->stream));
   } else {
     if (chunk == 0) rig_enqueue_prep(h);
@@ -1645,7 +1551,8 @@ static int rig_wait(cc_rig* h, RigRun* r) {
   CC_HIP(hipSetDevice(h->device));
   bool wait_failed = false;
   const bool lean_run = r->persist && h->persist_w_ok && h->stream2 != nullptr;   // (what rig_launch put on two streams)
-  if (int rc = ((h->comm || h->big) ? rig_read_ctl(h, &r->st, &wait_failed) : rig_wait_published(h, &r->st, &wait_failed, lean_run))) return rc;
+  const auto read_back = [&] { return rig_read_ctl(h, &r->st, &wait_failed); };
+  if (int rc = ((h->comm || h->big) ? read_back() : wait_published(h, lean_run ? h->stream2 : nullptr, &r->st, &wait_failed, "the rig solver", read_back))) return rc;
   if (r->st.done) { h->last_st = r->st; h->st_known = true; if (r->persist && !wait_failed) h->lean_strikes = 0; }
   if (wait_failed && r->persist) {
     // The lean form keeps the starting point intact: cc_rig_solve runs the solve again, three kernels per iteration, and this
@@ -1685,31 +1592,6 @@ static int rig_wait(cc_rig* h, RigRun* r) {
   return 0;
 }
 
-static int rig_finish(cc_rig* h, RigRun* r, cc_summary* summary) {
-  const LmCtl& st = r->st;
-  CC_HIP(hipSetDevice(h->device));
-  if (summary) {
-    cc_iteration* user_log = summary->log;
-    const int cap = summary->log_capacity;
-    summary->iterations = st.iter;
-    summary->successful_steps = st.n_success;
-    summary->termination = st.term;
-    summary->initial_cost = st.initial_cost;
-    summary->final_cost = st.x_cost;
-    summary->sweeps = st.sweeps;
-    const int n = user_log ? std::min(std::min(st.log_len, cap), h->d.log_cap) : 0;
-    summary->log_len = n;
-    if (n > 0) CC_HIP(hipMemcpy(user_log, h->d.log, (size_t)n * sizeof(cc_iteration), hipMemcpyDeviceToHost));
-    summarise_probes(h->events, r->profile ? h->event_kind : std::vector<int>(), h->event_round, st.iter, summary,
-                     [](float* ms, hipEvent_t a, hipEvent_t b) { return hipEventElapsedTime(ms, a, b) == hipSuccess; });
-    summary->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - r->t0).count();
-  }
-  for (auto e : h->events) hipEventDestroy(e);
-  h->events.clear();
-  h->event_kind.clear();
-  h->event_round.clear();
-  return CC_OK;
-}
 }  // namespace cc
 
 extern "C" {
@@ -1725,33 +1607,24 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
   // What the DEVICE has said about lean solves lately (persist_device_try, cc_common.hpp): a one-shot caller's handle is new
   // every call, so after a give-up the device's back-off window -- not this handle's memory -- keeps the next solves on the
   // three-kernel form; one solve probes the lean form again when the window is over.
-  const bool lean_wanted = h->persist_w_ok && !h->inner_on && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1;
-  bool lean_tried = false;
-  if (lean_wanted) {
-    lean_tried = persist_device_try(h->device, 1);
-    r.no_persist = !lean_tried;
-  }
+  // (whatever ends the admitted probe is reported once: PersistProbe, cc_solve_host.hpp -- a launch that fails is over too)
+  const bool lean_wanted = rig_lean_eligible(h, r.profile);
+  PersistProbe probe(h->device, 1, lean_wanted && persist_device_try(h->device, 1));
+  r.no_persist = lean_wanted && !probe.open;
   // (the lean form is two launches that wait for each other inside their kernels: one such solve at a time per device and
   // process -- persist_mutex, cc_common.hpp; a second host thread waits here instead of inside a kernel for 1.3 s)
   std::unique_lock<std::mutex> lean_lock(persist_mutex(h->device), std::defer_lock);
   for (int chunk = 0;; ++chunk) {
-    if (chunk == 0 && !r.no_persist && h->persist_w_ok && !h->inner_on && !r.profile && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)
-      lean_lock.lock();
-    if (int rc = rig_launch(h, &r, chunk)) {
-      if (chunk == 0 && lean_tried) persist_device_gave_up(h->device, 1);   // (a probe that never started is over too)
-      return rc;
-    }
+    if (chunk == 0 && !r.no_persist && rig_lean_eligible(h, r.profile)) lean_lock.lock();
+    if (int rc = rig_launch(h, &r, chunk)) return rc;
     if (chunk == 0) hp.mark("launch0");
-    if (int rc = rig_wait(h, &r)) {
-      if (chunk == 0 && lean_tried && r.persist) persist_device_gave_up(h->device, 1);   // (the probe is over, whatever ended it)
-      return rc;
-    }
+    if (int rc = rig_wait(h, &r)) return rc;
     // (a lean solve that gave up: its control launch on the second stream may still be queued or spinning -- the lock is kept
     // until both streams have drained below, or another thread's lean solve would start next to that late control workgroup)
     if (lean_lock.owns_lock() && !r.rerun) lean_lock.unlock();
     if (chunk == 0) hp.mark("wait0");
-    if (r.rerun) persist_device_gave_up(h->device, 1);
-    else if (chunk == 0 && lean_tried && r.persist) persist_device_completed(h->device, 1);
+    if (r.rerun) probe.gave_up();
+    else if (r.persist) probe.completed();
     if (r.rerun) {
       // The lean persistent launch could not get every workgroup resident (a device shared with another process, or the
       // control launch not scheduled next to the workers): a wait inside it gave up after 1.3 s. Frame poses go back to
@@ -1777,7 +1650,7 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
   }
   hp.mark("chunks");
   h->ran_form = r.persist ? 2 : 0;
-  const int rc_fin = rig_finish(h, &r, summary);
+  const int rc_fin = finish_summary(h, &r, summary);
   hp.mark("finish");
   return rc_fin;
 }
@@ -1785,17 +1658,13 @@ int cc_rig_solve(cc_rig* h, const cc_options* opt, cc_summary* summary) {
 int cc_rig_solver_form(cc_rig* h) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_solver_form: NULL handle");
-  if (!(h->persist_w_ok && !h->inner_on && !h->comm && !h->exchange && !h->big && h->co_resident <= 1)) return 0;
-  return 2;
+  return rig_lean_eligible(h, false) ? 2 : 0;
 }
 
 int cc_rig_solver_status(cc_rig* h, int32_t* form, int32_t* reruns, char* note, int32_t note_capacity) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_solver_status: NULL handle");
-  if (form) *form = cc_rig_solver_form(h);
-  if (reruns) *reruns = h->form_reruns;
-  if (note && note_capacity > 0) std::snprintf(note, (size_t)note_capacity, "%s", h->form_note.c_str());
-  return CC_OK;
+  return solver_status(h, cc_rig_solver_form(h), form, reruns, note, note_capacity);
 }
 
 int cc_rig_set_inner_iterations(cc_rig* h, int32_t enable, double tolerance) {
@@ -1809,7 +1678,7 @@ int cc_rig_set_inner_iterations(cc_rig* h, int32_t enable, double tolerance) {
     if (int rc = rig_inner_alloc(h)) return rc;
     CC_HIP(hipStreamSynchronize(h->stream));   // (the zeroed state, before a later status read)
   }
-  if ((enable != 0) != h->inner_on) rig_drop_graphs(h);   // (the hook's launches are part of a captured round)
+  if ((enable != 0) != h->inner_on) drop_graphs(h);   // (the hook's launches are part of a captured round)
   h->inner_on = enable != 0;
   h->inner_tol = tolerance;
   return CC_OK;
@@ -1959,7 +1828,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
   if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
-  rig_drop_graphs(h);
+  drop_graphs(h);
   if (int rc = comm_create(id, rank, nranks, &h->comm)) return rc;
   h->d.comm = 1; h->d.rank = rank; h->d.nranks = nranks;
   // a camera is part of the problem if ANY rank observes it: sum the per-rank "seen" flags
@@ -1979,13 +1848,8 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
 
 int cc_rig_exchange_export(cc_rig* h, uint8_t handle[64]) {
   using namespace cc;
-  if (!h || !handle) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_export: NULL argument");
-  CC_HIP(hipSetDevice(h->device));
-  CC_HIP(hipStreamSynchronize(h->stream));
-  rig_drop_graphs(h);
-  mailbox_release(&h->mailbox);
+  if (int rc = exchange_export_begin(h, handle, "cc_rig_exchange_export")) return rc;
   h->d.x = P2pDev{};
-  h->exchange = false;
   int k0 = 0, k1 = 0;
   rig_exchange_bounds(h, &k0, &k1);
   return mailbox_export(&h->mailbox, k0, k1, handle);
@@ -2001,7 +1865,7 @@ int cc_rig_exchange_attach(cc_rig* h, int32_t rank, int32_t nranks, const uint8_
   if (h->comm) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: an RCCL communicator is already attached");
   if (h->C > 128) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_attach: at most 128 cameras with the mailbox exchange");
   CC_HIP(hipSetDevice(h->device));
-  rig_drop_graphs(h);
+  drop_graphs(h);
   if (int rc = mailbox_attach(&h->mailbox, rank, nranks, handles, &h->d.x)) return rc;
   h->d.comm = 1; h->d.rank = rank; h->d.nranks = nranks;
   h->exchange = true;
@@ -2256,7 +2120,7 @@ int cc_rig_optimize_multi(const cc_options* opt, int32_t n_devices, const int32_
     if (all_done) break;
     if (any_done) rc = fail(CC_ERR_STATE, "cc_rig_optimize_multi: the shards disagree about termination");
   }
-  if (!rc) rc = rig_finish(hs[0], &runs[0], summary);
+  if (!rc) rc = finish_summary(hs[0], &runs[0], summary);
   for (int r = 0; r < n && !rc; ++r) {
     const int64_t f0 = first[(size_t)r];
     rc = cc_rig_get_state(hs[(size_t)r], r == 0 ? cam_q : nullptr, r == 0 ? cam_t : nullptr, frame_q + 4 * f0, frame_t + 3 * f0,

@@ -116,7 +116,7 @@ def test_every_rig_kernel_is_a_named_form():
     assert not any(n.startswith("k_rig_sweep<") or n.startswith("k_rig_persist<") or n == "k_rig_persist" for n in names)
     # the file split of round 5: the host side + launches stay under 2,500 lines, no part above 2,000
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "camera_calibrator_amd", "csrc")
-    sizes = {f: sum(1 for _ in open(os.path.join(root, f))) for f in ("cc_rig.hip", "cc_rig_sweeps.hpp", "cc_rig_steps.hpp", "cc_rig_big.hpp", "cc_rig_lean.hpp")}
+    sizes = {f: sum(1 for _ in open(os.path.join(root, f))) for f in ("cc_rig.hip", "cc_rig_sweeps.hpp", "cc_rig_steps.hpp", "cc_rig_big.hpp", "cc_rig_lean.hpp", "cc_solve_host.hpp")}
     assert sizes["cc_rig.hip"] < 2500 and max(sizes.values()) < 2500, sizes
 
 
