@@ -137,25 +137,36 @@ __device__ __forceinline__ void gram_rows(const double* stage, int lane, d4& acc
   }
 }
 
-// The same contraction with its schedule pinned: all sixteen operand reads are issued first, then the sixteen matrix
-// products, each waiting only for its own operand (the scheduler may not move anything across the barrier between the
-// two groups). Inside the persistent kernel's round loop the compiler otherwise interleaves read / wait / product one
-// operand at a time -- every product then sits behind a full LDS round trip (13.5 us instead of 8.4 for the two passes
-// of a 500-point frame at four waves per SIMD).
-__device__ __forceinline__ void gram_rows_ahead(const double* stage, int lane, d4& acc0, d4& acc1) {
+// The two halves of the same contraction, for a caller that pins its schedule: the sixteen operand reads of gram_rows,
+// and the sixteen matrix products on operands already in registers (same operands, same order, same accumulators).
+__device__ __forceinline__ void gram_operands(const double* stage, int lane, double* a) {
   const int c = lane & 15, sub = lane >> 4;
-  double a[16];
 #pragma unroll
   for (int m = 0; m < 16; ++m) {
     const int r = 4 * m + sub;
     a[m] = stage[r * 16 + (((c >> 1) ^ (r & 7)) << 1) + (c & 1)];
   }
-  __builtin_amdgcn_sched_barrier(0);
+}
+
+__device__ __forceinline__ void gram_products(const double* a, d4& acc0, d4& acc1) {
 #pragma unroll
   for (int m = 0; m < 16; m += 2) {
     acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], a[m], acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m + 1], a[m + 1], acc1, 0, 0, 0);
   }
+}
+
+// gram_rows with its schedule pinned: all sixteen operand reads are issued first, then the sixteen matrix products, each
+// waiting only for its own operand (the scheduler may not move anything across the barrier between the two groups).
+// Inside the persistent kernel's round loop the compiler otherwise interleaves read / wait / product one operand at a
+// time -- every product then sits behind a full LDS round trip (13.5 us instead of 8.4 for the two passes of a 500-point
+// frame at four waves per SIMD). (Both row sets of a pass staged in front of ONE burst of 32 products -- the v-rows written
+// behind the u-operand reads -- was measured and dropped: DESIGN.md 4.8.)
+__device__ __forceinline__ void gram_rows_ahead(const double* stage, int lane, d4& acc0, d4& acc1) {
+  double a[16];
+  gram_operands(stage, lane, a);
+  __builtin_amdgcn_sched_barrier(0);
+  gram_products(a, acc0, acc1);
   __builtin_amdgcn_sched_barrier(0);
 }
 

@@ -20,8 +20,9 @@
 // Seams are self-validating 8-byte words {epoch32 : half of a double}, stored and polled with agent-scope (sc1)
 // accesses: an aligned 8-byte store is single-copy atomic, so there is no flag, no fence, no drain (MI355X guide,
 // Guideline 16 R2). Sums over rows run in a fixed order: results do not depend on timing or placement. Every wait is
-// bounded (the first round's by 10.5 ms, later ones by 1.3 s; 10 s as a rank of an exchange); one that gives up sets the
-// failure word, everybody leaves, and a handle alone on its device runs the solve again with two kernels per iteration.
+// bounded by 2^shift ticks of the 100 MHz wall clock (PersistDev::first_shift / timeout_shift: the first round's waits by
+// 10.5 ms, later ones by 1.3 s, all of them by 10.7 s as a rank of an exchange); one that gives up sets the failure word,
+// everybody leaves, and a handle alone on its device runs the solve again with two kernels per iteration.
 #include "cc_intrinsics_persist.hpp"
 #include "cc_persist_dev.hpp"
 
@@ -285,21 +286,10 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       }
       __syncthreads();
     }
-    // the workers eliminated with unit scales on the shared columns: the Jacobi scaling of the reduced system happens here
-    if (tid < 63) {
-      double f2;
-      if (tid < 45) {
-        int j = 0, rem = tid;
-        while (rem >= 9 - j) { rem -= 9 - j; ++j; }
-        f2 = s_ss[j] * s_ss[j + rem];
-      } else if (tid < 54) {
-        f2 = s_ss[tid - 45];
-      } else {
-        f2 = s_ss[tid - 54] * s_ss[tid - 54];
-      }
-      sv[tid] *= f2;
-    }
-    __syncthreads();
+    // (the workers eliminated with unit scales on the shared columns: the Jacobi scaling of the reduced system happens in
+    // wave 0's row build below -- entry (j, k) times s_j s_k, right-hand side times s_j, diagonal for the damping times s_j s_j,
+    // the products a 63-thread pass used to leave in LDS behind a barrier of its own; the gradient test reads what it always
+    // read, the unscaled PC_GS and PC_GMAXP)
     if (wave == 0) {
       // (the lane index of THIS round, opaque to the compiler: with the plain one it computes the nine per-lane selects and unit-row
       // constants of the pinned coordinates once, before the round loop, and keeps them in registers it does not have -- the
@@ -316,24 +306,26 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       bool ok = !(sv[PC_FAIL] > 0.0);
       double x[9];
       {
+#pragma clang fp contract(off)   // (the scaled entries were rounded on their way through LDS: no product may fuse into the damping's sum)
         // row `lane` of the damped reduced system (sv[0..44]: upper triangle, row-major pairs j <= k). Built and solved
         // whether or not the tests above let the solve go on: nothing else waits on this wave, and a branch on `go`
         // would put the gradient maximum in front of the factorisation.
         const int i = lane < 9 ? lane : 8;
         const bool pin_i = (mask >> i) & 1u;
-        const double damp = clampd(sv[PC_HDIAG + i], o.min_lm_diagonal, o.max_lm_diagonal) / radius;   // (ONE division per lane)
+        const double si = s_ss[i];
+        const double damp = clampd(sv[PC_HDIAG + i] * (si * si), o.min_lm_diagonal, o.max_lm_diagonal) / radius;   // (ONE division per lane)
         double a[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
           const int kk = k <= i ? k : i;                           // (entries beyond the diagonal: ignored, keep them finite)
           const int idx = kk * 9 - kk * (kk - 1) / 2 + (i - kk);   // pair (kk, i)
-          double v = sv[idx];
+          double v = sv[idx] * (s_ss[kk] * si);
           if (k == i) v += damp;
           const bool pin_k = (mask >> kk) & 1u;
           if (pin_i || pin_k) v = (k == i) ? 1.0 : 0.0;           // SubsetManifold: unit row / column, zero right-hand side
           a[k] = v;
         }
-        const double b = pin_i ? 0.0 : sv[PC_B + i];
+        const double b = pin_i ? 0.0 : sv[PC_B + i] * si;
         ok = chol_solve_rows<9>(a, b, x) && ok;
 #pragma unroll
         for (int j = 0; j < 9; ++j) ok = ok && isfinite(x[j]);
@@ -354,9 +346,11 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
         s_bc[0] = (double)((go ? 0 : 1) | (go && ok ? 2 : 0) | (hit ? 4 : 0) | (cur << 3));
         s_bc[1] = radius;
       }
+      // the broadcast leaves from THIS wave: it reads back what its own lanes have just written (a wave's LDS operations execute
+      // in order), no workgroup barrier between the solve and the store the workers are waiting for
+      wave_lds_fence();
+      if (lane < 22) ag_st(Q.xbox + lane, granule(erow, s_bc[lane >> 1], lane & 1));
     }
-    __syncthreads();
-    if (tid < 22) ag_st(Q.xbox + tid, granule(erow, s_bc[tid >> 1], tid & 1));
     if (tid == 0) {
       // (on the control block in LDS: only the fields lm_finalize touches move, not 144 bytes each way)
       double gmax = sv[PC_GMAXP];
