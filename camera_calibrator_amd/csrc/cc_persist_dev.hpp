@@ -28,7 +28,8 @@ __device__ __forceinline__ double ungranule(u64 lo, u64 hi) { return __longlong_
 __device__ __forceinline__ double persist_spec_radius(double radius, double max_radius) { return fmin(max_radius, radius / (1.0 / 3.0)); }
 
 // One wave waits until the n doubles of a broadcast box carry `tag` and leaves them in dst[0..n) (LDS); lane l polls
-// word l. false: gave up (timeout, or somebody else already failed); the failure word is set.
+// word l. false: gave up (timeout, or somebody else already failed); the failure word is set. (rig_bcast_wait, cc_rig_lean.hpp,
+// is the same loop with several words per lane: keep the two in step.)
 __device__ __forceinline__ bool bcast_wait(const u64* box, unsigned tag, int n, double* dst, unsigned* fail, int lane, int tshift) {
   const bool mine = lane < 2 * n;
   const u64* p = box + (mine ? lane : 0);

@@ -423,6 +423,22 @@ static int lds_attr(int device, const void* fn, int bytes) {
   return 0;
 }
 
+// The elimination kernel of a problem: kcm / kmode / fmode as in RigDev (compact K records imply intrinsics, and neither goes
+// with the frame form), small: ND <= 8 * 64, eight direct sums per lane suffice. rig_layout sets the LDS attribute by walking
+// this function over its arguments and rig_enqueue_round launches what it returns, so a variant cannot be in one list only.
+static void (*rig_elim_kernel(bool kcm, bool kmode, bool fmode, bool small))(RigDev) {
+  if (kcm) return small ? k_rig_elim<true, 8, false, true> : k_rig_elim<true, kRigDirectPerLane, false, true>;
+  if (kmode) return small ? k_rig_elim<true, 8> : k_rig_elim<true, kRigDirectPerLane>;
+  if (fmode) return small ? k_rig_elim<false, 8, true> : k_rig_elim<false, kRigDirectPerLane, true>;
+  return small ? k_rig_elim<false, 8> : k_rig_elim<false, kRigDirectPerLane>;
+}
+
+// The lean worker kernel for `teams` frames per workgroup, with its thread count
+struct RigWorkerKernel { void (*fn)(RigDev, RigPersistDev); int threads; };
+static RigWorkerKernel rig_persist_w_kernel(int teams) {
+  return {teams == 1 ? k_rig_persist_w<1> : teams == 2 ? k_rig_persist_w<2> : k_rig_persist_w<4>, teams * 256};
+}
+
 // Shared-block layout for the cameras in `seen_any` (observed by at least one rank): which camera owns which
 // columns, the tile grid of the Schur products, the direct-sum table -- and every buffer whose size depends on
 // them. Called by create (with the locally observed cameras) and again by the multi-GPU attach calls when
@@ -618,14 +634,10 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     drop_graphs(h);
     return 0;
   }
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<false, 8>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<false, 8, true>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<false, kRigDirectPerLane, true>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<true, 8>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<false, kRigDirectPerLane>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<true, kRigDirectPerLane>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<true, 8, false, true>), (int)h->elim_lds)) return rc_;
-  if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_elim<true, kRigDirectPerLane, false, true>), (int)h->elim_lds)) return rc_;
+  const bool elim_forms[4][3] = {{false, false, false}, {false, false, true}, {false, true, false}, {true, true, false}};   // kcm, kmode, fmode
+  for (const auto& f : elim_forms)
+    for (const bool small : {false, true})
+      if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(rig_elim_kernel(f[0], f[1], f[2], small)), (int)h->elim_lds)) return rc_;
   if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_reduce<0>), (int)h->solve_lds)) return rc_;
   if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_reduce<3>), (int)h->solve_lds)) return rc_;
   if (int rc_ = lds_attr(h->device, reinterpret_cast<const void*>(k_rig_solve<0>), (int)h->solve_lds)) return rc_;
@@ -642,7 +654,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     comp.push_back(d.pc_fail);
     comp.push_back(d.pc_gmax);
     RigPersistDev& q = h->pq;
-    q.G = (int32_t)((F + 3) / 4); q.K = (int32_t)comp.size(); q.KS = 4 + S; q.NB = 2 + S + 32 * (int32_t)C;
+    q.K = (int32_t)comp.size(); q.KS = 4 + S; q.NB = 2 + S + 32 * (int32_t)C;
     // the lean form (k_rig_persist_w) takes the fewest frames per workgroup that still leave every XCD a compute unit for the
     // control workgroup: fewer frames per compute unit = more of the chip in the sweep
     const bool lean_shape = (int)comp.size() <= kRpwMaxK;
@@ -666,8 +678,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
       slots[comp.size() - 1] = -2;
       if (int rc = dev_upload(h, &q.slots, slots)) return rc;
     }
-    const int Gmax = q.G;
-    const size_t n_s = (size_t)Gmax * q.KS * 2, n_a = (size_t)(2 + S) * 2, n_r = (size_t)Gmax * q.K * 2, n_c = (size_t)q.K * 2, n_y = (size_t)q.NB * 2;
+    const size_t n_s = (size_t)q.G * q.KS * 2, n_a = (size_t)(2 + S) * 2, n_r = (size_t)q.G * q.K * 2, n_c = (size_t)q.K * 2, n_y = (size_t)q.NB * 2;
     u64* base = nullptr;
     h->p_box_words = n_s + n_a + 2 * n_r + 2 * n_c + n_y + 1;
     if (int rc = dev_zeroed(h, &base, h->p_box_words)) return rc;
@@ -679,18 +690,13 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     hipError_t e1 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
     if (e1 != hipSuccess) (void)hipGetLastError();
     if (!h->d_cam_backup) { if (int rc = dev_zeroed(h, &h->d_cam_backup, (size_t)C * 8)) return rc; }
-    h->persist_w_ok = false;
     if (e1 == hipSuccess && lean_shape && q.G <= 255 && cus >= 256) {
       int pw = 0;
       const int lb = rpw_lds_doubles(h->p_teams) * 8;
-      const void* kw = h->p_teams == 1 ? reinterpret_cast<const void*>(k_rig_persist_w<1>) : h->p_teams == 2 ? reinterpret_cast<const void*>(k_rig_persist_w<2>)
-                                                                                           : reinterpret_cast<const void*>(k_rig_persist_w<4>);
-      hipError_t e2 = hipFuncSetAttribute(kw, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
+      const RigWorkerKernel kw = rig_persist_w_kernel(h->p_teams);
+      hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kw.fn), hipFuncAttributeMaxDynamicSharedMemorySize, lb);
       if (e2 == hipSuccess) e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rig_persist_ctl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rig_persist_ctl_lds(h->solve_lds, d));
-      if (e2 == hipSuccess)
-        e2 = h->p_teams == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, k_rig_persist_w<1>, 256, (size_t)lb)
-           : h->p_teams == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, k_rig_persist_w<2>, 512, (size_t)lb)
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, k_rig_persist_w<4>, 1024, (size_t)lb);
+      if (e2 == hipSuccess) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pw, kw.fn, kw.threads, (size_t)lb);
       if (e2 != hipSuccess) (void)hipGetLastError();
       h->persist_w_ok = e2 == hipSuccess && pw >= 1;
       // Where it FITS is not where it PAYS (round 6, profiles/r06/lean_vs_three_kernel_grid.txt: 2 and 4 cameras x 256 .. 1020
@@ -847,15 +853,7 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     return 0;
   }
   { Probe p(h, CC_K_ELIM, profile);
-    const bool small = d.ND <= 8 * 64;
-    if (d.kcm && small) hipLaunchKernelGGL((k_rig_elim<true, 8, false, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (d.kcm) hipLaunchKernelGGL((k_rig_elim<true, kRigDirectPerLane, false, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (d.kmode && small) hipLaunchKernelGGL((k_rig_elim<true, 8>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (d.kmode) hipLaunchKernelGGL((k_rig_elim<true, kRigDirectPerLane>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (d.fmode && small) hipLaunchKernelGGL((k_rig_elim<false, 8, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (d.fmode) hipLaunchKernelGGL((k_rig_elim<false, kRigDirectPerLane, true>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else if (small) hipLaunchKernelGGL((k_rig_elim<false, 8>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d);
-    else hipLaunchKernelGGL((k_rig_elim<false, kRigDirectPerLane>), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d); }
+    hipLaunchKernelGGL(rig_elim_kernel(d.kcm != 0, d.kmode != 0, d.fmode != 0, d.ND <= 8 * 64), dim3(d.nblk), dim3(256), h->elim_lds, h->stream, d); }
   // (every block of the fused launch must be resident at once: its grid comes from rig_size_reduce_grid, rig_begin)
   const unsigned rblocks = (unsigned)std::max(1, h->reduce_blocks);
   if (h->comm) {
@@ -1411,7 +1409,7 @@ namespace cc {
 // A solve in phases (cf. cc_intrinsics.hip): begin -> { launch a chunk -> wait } ... -> finish, so that one host
 // thread can drive several handles (devices) in lock step.
 struct RigRun : SolveRunBase {
-  bool persist = false;   // this solve runs as ONE launch of k_rig_persist / k_rig_persist_w
+  bool persist = false;   // this solve runs in the lean persistent form: one launch of k_rig_persist_w, one of k_rig_persist_ctl
   bool no_persist = false;   // (a rerun after that launch could not get its workgroups resident)
   bool rerun = false;        // set by rig_wait: the lean persistent launch gave up, nothing was written back
 };
@@ -1458,7 +1456,7 @@ static int rig_begin(cc_rig* h, const cc_options* opt, RigRun* r) {
 static int rig_launch(cc_rig* h, RigRun* r, int chunk) {
   CC_HIP(hipSetDevice(h->device));
   if (chunk == 0 && !r->no_persist && rig_lean_eligible(h, r->profile)) {
-    // the whole solve in one launch (k_rig_persist); the control workgroup publishes when it is over
+    // the whole solve in the lean persistent form (cc_rig_lean.hpp); the control workgroup publishes when it is over
     RigPersistDev q = h->pq;
     q.max_rounds = r->o.max_iterations + 2;
     q.timeout_shift = 27;   // 1.3 s of the 100 MHz wall clock
@@ -1491,16 +1489,13 @@ static int rig_launch(cc_rig* h, RigRun* r, int chunk) {
     // 32 workers need: seen at once on the first box tried.)
     q.gate = const_cast<unsigned long long*>(h->host_pub) + 22;
     const size_t lb = (size_t)rpw_lds_doubles(h->p_teams) * 8;
-    if (h->p_teams == 1) hipLaunchKernelGGL(k_rig_persist_w<1>, dim3((unsigned)q.G), dim3(256), lb, h->stream, h->d, q);
-    else if (h->p_teams == 2) hipLaunchKernelGGL(k_rig_persist_w<2>, dim3((unsigned)q.G), dim3(512), lb, h->stream, h->d, q);
-    else hipLaunchKernelGGL(k_rig_persist_w<4>, dim3((unsigned)q.G), dim3(1024), lb, h->stream, h->d, q);
+    const RigWorkerKernel kw = rig_persist_w_kernel(h->p_teams);
+    hipLaunchKernelGGL(kw.fn, dim3((unsigned)q.G), dim3((unsigned)kw.threads), lb, h->stream, h->d, q);
     CC_HIP(hipGetLastError());
-    if (q.gate) {
-      const auto tg = std::chrono::steady_clock::now();
-      const unsigned long long want = (unsigned long long)(q.epoch0 + 1u);
-      for (unsigned spins = 0; __atomic_load_n(const_cast<const unsigned long long*>(q.gate), __ATOMIC_ACQUIRE) != want; ++spins)
-        if ((spins & 0x3ffu) == 0x3ffu && std::chrono::steady_clock::now() - tg > std::chrono::milliseconds(5)) break;   // (not all resident: the workers will give up and the solve is rerun)
-    }
+    const auto tg = std::chrono::steady_clock::now();
+    const unsigned long long want = (unsigned long long)(q.epoch0 + 1u);
+    for (unsigned spins = 0; __atomic_load_n(const_cast<const unsigned long long*>(q.gate), __ATOMIC_ACQUIRE) != want; ++spins)
+      if ((spins & 0x3ffu) == 0x3ffu && std::chrono::steady_clock::now() - tg > std::chrono::milliseconds(5)) break;   // (not all resident: the workers will give up and the solve is rerun)
     if (!drop_control)
       hipLaunchKernelGGL(k_rig_persist_ctl, dim3((unsigned)kRigCtlCandidates), dim3(256), rig_persist_ctl_lds(h->solve_lds, h->d), h->stream2, h->d, q);
     CC_HIP(hipGetLastError());

@@ -560,7 +560,7 @@ __global__ __launch_bounds__(256) void k_rig_solve_big(RigDev P, double* Aglobal
 #pragma unroll
           for (int k = 15; k >= 0; --k) {
             if (k < nbk) {   // (uniform)
-              const double xk = readlane_d(bj, k) * s_inv[kb + k];
+              const double xk = lane_bcast(bj, k) * s_inv[kb + k];
               bj = lane == k ? xk : fma(-lcol[k], xk, bj);
             }
           }

@@ -4,42 +4,40 @@
 #pragma once
 
 // =============================================================================================
-// THE RIG SOLVE AS ONE PERSISTENT KERNEL (round 3; poses only, single GPU, at most four frames per compute unit).
-// TWO FORMS. This one, k_rig_persist, GLUES the three kernels' bodies together: AN EXPERIMENT, OFF BY DEFAULT (CC_RIG_PERSIST=1,
-// used where the lean form below does not fit): correct -- the rig test suite passes on it -- and SLOWER than the three
-// kernels it replaces: 81 against 47 us per iteration at BASELINE configs[3] size (profiles/r03/rig_persist_marks.jsonl).
-// The bodies need up to 444 registers per thread, so a compute unit holds ONE wave per SIMD: the sweep of a frame's groups
-// runs one after the other with every memory round trip exposed (25.6 us where the stand-alone sweep, sixteen waves deep,
-// takes 9), and pose update, elimination and solve step each run 1.3 - 2 x slower for the same reason.
-// The LEAN form further down (k_rig_persist_w + k_rig_persist_ctl: small rigs, the per-frame state in LDS, one wave per
-// group, the workers under 128 / 256 registers) is what runs BY DEFAULT where it fits: 39 us at configs[3] size. Seams,
-// control workgroup and host side are shared.
-// Three launches per LM iteration cost this path ~19 of its ~47 us at BASELINE configs[3] (ramp of a launch, dependent
-// read of the control block, the gap; profiles/r03/rig_c4_kernel_stats.csv): here ONE launch runs the whole solve, built
-// from the very functions the three kernels run (rig_update_body, rig_sweep_adj_body, rig_elim_body, rig_solve_block,
-// rig_candidates), with the seams of cc_intrinsics_persist.hip between them (cc_persist_dev.hpp: self-validating words,
-// no atomics, no flags, bounded waits).
-//   grid    : G = ceil(F / 4) worker workgroups + 1 control workgroup, 256 threads each, all resident (host: occupancy).
-//   worker b: frames 4b .. 4b + 3, one wave each, for the whole solve. Round: [broadcast B: step + camera records] ->
-//             pose update of its frames -> sweep of their groups (one wave: the groups of its frame one after the other)
-//             -> statistics row -> [broadcast A: decision] -> elimination of its four frames -> partial row, compacted
-//             to the K entries the reduced system uses -> posts it; then adds up ITS share of the K columns over all G
-//             rows (column c belongs to worker c mod G: every worker reads G x K / G words -- the column sums of
-//             k_rig_reduce, spread over the workers) and posts the sums.
+// THE RIG SOLVE IN ONE LAUNCH: k_rig_persist_w<TEAMS> + k_rig_persist_ctl (poses only, single GPU, small rigs: at most
+// kRpwMaxCO observed cameras, kRpwMaxS shared coordinates, 4 x 255 frames). It runs BY DEFAULT where it fits and pays
+// (rig_layout, cc_rig.hip): 39 us per iteration at BASELINE configs[3] size where the three kernels take 47 -- three
+// launches per LM iteration cost that path ~19 us (ramp of a launch, dependent read of the control block, the gap;
+// profiles/r03/rig_c4_kernel_stats.csv). (A glued form, the three kernels' bodies in one launch, existed in round 3 and
+// lost: cc_rig.hip, rig_layout, has its numbers; profiles/r03/rig_persist_marks.jsonl its timeline.)
+//   grid    : G = ceil(F / TEAMS) <= 255 worker workgroups of TEAMS x 256 threads on one stream (TEAMS = 1, 2 or 4 frames per
+//             workgroup: the fewest that fit), all resident (host: occupancy); kRigCtlCandidates control candidates of 256
+//             threads on a second stream, launched by the host once the last worker to start has stored the solve's tag
+//             into the pinned gate word. The first candidate to run claims the solve and is the control; the others leave.
+//   worker b: frames TEAMS b .. TEAMS b + TEAMS - 1, a team of four waves each, for the whole solve; the frame's state
+//             lives in LDS (poses in both buffers, frame record, the 16 x 16 blocks and compact records of its groups, Y, Z,
+//             Jacobi scales). Round: [broadcast B: step + camera records] -> pose update of its frames (sixteen lanes of a
+//             team's first wave) -> sweep (one WAVE per group, rig_sweep_adj_body<1, true>) -> statistics row -> elimination
+//             of its frames ON THE ASSUMED DECISION (candidate accepted, radius at its clamp; one wave per frame, the compact
+//             row built straight from the slot table) -> posts the row (pbox); adds up ITS share of the K columns over all
+//             G rows (column c belongs to worker c mod G) and posts the sums (pcbox) -> [broadcast A: decision]. The
+//             assumption held: next round. It did not (first round, rejected step, other radius): eliminates the point
+//             the control named a second time and posts to rbox / cbox.
 //   control : owns the trust-region state. Gathers the statistics rows -> decision (first round: Jacobi scales of the
-//             shared columns, |x|, lm_init -- what k_rig_init does) -> broadcast A; gathers the K column sums ->
-//             reduced solve, candidates, records (rig_solve_block, unchanged) -> broadcast B.
-// What a workgroup writes to global memory for its own later use (poses, frame records, group blocks, Y, partial row)
-// it reads back itself: plain stores and loads on one compute unit. Sums over rows run in a fixed order.
-// A wait that gives up sets the failure word (arrive[3]): nothing further happens, the host returns CC_ERR_COMM and the
-// handle goes back to the three-kernel form.
+//             shared columns, |x|, lm_init -- what k_rig_init does) -> broadcast A; gathers the K column sums (pcbox if the
+//             assumption held, else cbox) -> reduced solve, candidates, records (rig_solve_block, unchanged) -> broadcast B.
+// Seams (cc_persist_dev.hpp): everything that crosses workgroups travels as self-validating words {tag : half of a double},
+// tag = epoch0 + round + 1 -- no atomics, no flags, bounded waits. What a workgroup writes for its own later use it keeps in
+// LDS; only the accepted poses go back to global memory when the solve is over. Sums over rows run in a fixed order.
+// A wait that gives up sets the failure word (arrive[3]) and every other wait follows: the workers write nothing back, the
+// control ends the solve with CC_FAILURE_EXCHANGE, and the host runs the solve again in the three-kernel form (rig_wait).
 // =============================================================================================
 struct RigPersistDev {
   u64* sbox;            // [G][KS][2]  statistics rows: cost, model term, step^2, |x|^2, S diagonal sums (first round)
   u64* abox;            // [2 + S][2]  broadcast A: flags (1 done | cur << 3), radius, Jacobi scales of the shared columns (first round)
   u64* rbox;            // [G][K][2]   elimination rows (compacted)
   u64* cbox;            // [K][2]      column sums
-  u64* pbox, *pcbox;    // the same two for the elimination on the ASSUMED decision (k_rig_persist_w; null: nobody assumes)
+  u64* pbox, *pcbox;    // the same two for the workers' elimination on the ASSUMED decision
   u64* ybox;            // [NB][2]     broadcast B: flags (1 done | 2 step valid | cur << 3), radius, step[S], camera records [C][32]
   const int32_t* comp;  // [K] entry of the partial-row layout behind compact index k (the last two: failures, gradient maximum)
   const int32_t* slots; // [K] the same entries for k_rig_persist_w: 1 << 30 | p << 8 | q: sum_i Z[i][p] Z[i][q]; c << 16 | offset: entry of observed
@@ -48,15 +46,19 @@ struct RigPersistDev {
   unsigned epoch0;      // tags: epoch0 + round + 1 (boxes are zeroed when they would wrap)
   unsigned* claim;      // [1] the control candidate that exchanges epoch0 + 1 in first is the control workgroup (k_rig_persist_ctl)
   unsigned long long* gate;   // pinned host word: the worker that finds all G workers started stores epoch0 + 1 into it and the HOST then
-                              //   launches the control (rig_launch); null: no gate (the candidates run when they run)
+                              //   launches the control (rig_launch)
   int32_t max_rounds, timeout_shift, first_shift;   // (first_shift: the workers' wait for the control's FIRST broadcast)
-};
+};   // (every pointer is set for every launch: boxes, tables and claim word by rig_layout, the gate by rig_launch; the kernels' tests of
+     //  pbox and gate stay only because the compiled kernels change without them)
 
 constexpr int kRigPersistMaxS = 48;     // shared coordinates (8 optimised cameras)
 constexpr int kRigPersistMaxC = 9;      // cameras (records travel in broadcast B)
 constexpr int kRigPersistMaxNB = 2 + kRigPersistMaxS + 32 * kRigPersistMaxC;   // (the control workgroup's own copies are sized for 48 coordinates; the workers take kRpwMaxS)
 
 // One wave waits until the n doubles of a broadcast box carry `tag` and leaves them in dst[0..n) (LDS). false: gave up.
+// This is bcast_wait (cc_persist_dev.hpp) with several words per lane instead of one: the two must stay in step -- timeout,
+// failure word, spin cadence, word layout. (One template for both was tried: every form that left k_intr_persist's
+// instructions alone cost k_rig_persist_w<4> two more spilled scalar registers.)
 __device__ __forceinline__ bool rig_bcast_wait(const u64* box, unsigned tag, int n, double* dst, unsigned* fail, int tshift) {
   int lane = threadIdx.x & 63;
   asm volatile("" : "+v"(lane));   // (a fresh copy: the eleven word addresses of a lane are not worth keeping across a round)
@@ -138,8 +140,8 @@ __device__ __forceinline__ bool rig_gather_cols(const u64* box, int G, int rowle
   return s_good != 0;
 }
 
-// The control workgroup of the persistent rig kernels (256 threads; dynamic LDS: the solve step's, rig_solve_block): block G of
-// k_rig_persist, or a launch of its own next to the lean workers of k_rig_persist_w (k_rig_persist_ctl).
+// The control workgroup of the lean persistent form (256 threads; dynamic LDS: the solve step's, rig_solve_block, then the
+// reduced row and the destination tables): the candidate of k_rig_persist_ctl that claimed the solve.
 __device__ __forceinline__ void rig_persist_control(const RigDev& P, const RigPersistDev& Q, char* smem_raw) {
   __shared__ double s_bc[kRigPersistMaxNB];     // broadcast B of this round: flags, radius, step, camera records
   __shared__ double s_a[2 + kRigPersistMaxS];   // broadcast A
@@ -150,181 +152,177 @@ __device__ __forceinline__ void rig_persist_control(const RigDev& P, const RigPe
   const int tid = threadIdx.x;
   const int S = P.S, C = P.C, G = Q.G, K = Q.K, KS = Q.KS, NB = Q.NB;
   unsigned* fail = P.arrive + 3;
-    // =========================================================================== control workgroup
-    __shared__ LmCtl s_ctl;
-    __shared__ cc_iteration s_rec;
-    __shared__ double s_tot[4 + kRigPersistMaxS];
-    __shared__ int s_has_rec, s_hit;
-    double* smem = reinterpret_cast<double*>(smem_raw);
-    double* vl = smem + (size_t)S * ((S + 1) | 1) + 5 * 128;   // [PC + 32] the reduced row in the layout rig_solve_block reads, behind its own LDS
-    if (tid == 0) s_ctl = *P.ctl;   // (zeros: rig_begin)
-    for (int i = tid; i < P.PC + 32; i += 256) vl[i] = 0.0;   // entries the compact rows never touch stay zero
-    // the solve step's destination tables, copied to LDS once: rig_solve_block walks them every round, and here nothing
-    // but this workgroup's latency is on the critical path (flat loads of LDS addresses through the same RigDev fields)
-    RigDev Pc = P;
+  __shared__ LmCtl s_ctl;
+  __shared__ cc_iteration s_rec;
+  __shared__ double s_tot[4 + kRigPersistMaxS];
+  __shared__ int s_has_rec, s_hit;
+  double* smem = reinterpret_cast<double*>(smem_raw);
+  double* vl = smem + (size_t)S * ((S + 1) | 1) + 5 * 128;   // [PC + 32] the reduced row in the layout rig_solve_block reads, behind its own LDS
+  if (tid == 0) s_ctl = *P.ctl;   // (zeros: rig_begin)
+  for (int i = tid; i < P.PC + 32; i += 256) vl[i] = 0.0;   // entries the compact rows never touch stay zero
+  // the solve step's destination tables, copied to LDS once: rig_solve_block walks them every round, and here nothing
+  // but this workgroup's latency is on the critical path (flat loads of LDS addresses through the same RigDev fields)
+  RigDev Pc = P;
+  {
+    int32_t* t_tile = reinterpret_cast<int32_t*>(vl + P.PC + 32);
+    int32_t* t_dd = t_tile + P.nT * 256;
+    int32_t* t_dn = t_dd + P.ND;
+    int16_t* t_sa = reinterpret_cast<int16_t*>(t_dn + P.ND);
+    int16_t* t_sb = t_sa + P.ND;
+    for (int i = tid; i < P.nT * 256; i += 256) t_tile[i] = P.tile_dst[i];
+    for (int i = tid; i < P.ND; i += 256) { t_dd[i] = P.dir_dst[i]; t_dn[i] = P.dir_next[i]; t_sa[i] = P.dir_sa[i]; t_sb[i] = P.dir_sb[i]; }
+    Pc.tile_dst = t_tile; Pc.dir_dst = t_dd; Pc.dir_next = t_dn; Pc.dir_sa = t_sa; Pc.dir_sb = t_sb;
+  }
+  __syncthreads();
+  {   // records of the starting point (k_rig_records) -> broadcast B of round 0
+    double a, b;
+    rig_candidates(P, nullptr, nullptr, false, s_ctl.cur, s_ctl.cur, a, b);
+  }
+  __syncthreads();
+  bool failed = false;
+  for (int round = 0; round < Q.max_rounds; ++round) {
+    const unsigned e = Q.epoch0 + (unsigned)round + 1u;
+    const bool phase0 = round == 0;
+    // ---- broadcast B(e): what this round's sweep evaluates
+    if (tid == 0) {
+      s_bc[0] = (double)((s_ctl.done ? 1 : 0) | ((phase0 || s_ctl.step_valid) ? 2 : 0) | ((s_ctl.cur & 1) << 3));
+      s_bc[1] = s_ctl.radius;
+    }
+    if (!phase0 && tid < S) s_bc[2 + tid] = -smem[(size_t)S * ((S + 1) | 1) + tid];   // the shared step: -x of rig_solve_block (s_b)
+    if (phase0 && tid < S) s_bc[2 + tid] = 0.0;
+    for (int i = tid; i < 32 * C; i += 256) s_bc[2 + S + i] = P.camrec[i];
+    __syncthreads();
+    for (int w = tid; w < 2 * NB; w += 256) ag_st(Q.ybox + w, granule(e, s_bc[w >> 1], w & 1));
+    if (s_ctl.done) break;
+    // ---- statistics rows -> decision
+    const bool swept = phase0 || s_ctl.step_valid;
     {
-      int32_t* t_tile = reinterpret_cast<int32_t*>(vl + P.PC + 32);
-      int32_t* t_dd = t_tile + P.nT * 256;
-      int32_t* t_dn = t_dd + P.ND;
-      int16_t* t_sa = reinterpret_cast<int16_t*>(t_dn + P.ND);
-      int16_t* t_sb = t_sa + P.ND;
-      for (int i = tid; i < P.nT * 256; i += 256) t_tile[i] = P.tile_dst[i];
-      for (int i = tid; i < P.ND; i += 256) { t_dd[i] = P.dir_dst[i]; t_dn[i] = P.dir_next[i]; t_sa[i] = P.dir_sa[i]; t_sb[i] = P.dir_sb[i]; }
-      Pc.tile_dst = t_tile; Pc.dir_dst = t_dd; Pc.dir_next = t_dn; Pc.dir_sa = t_sa; Pc.dir_sb = t_sb;
-    }
-    __syncthreads();
-    {   // records of the starting point (k_rig_records) -> broadcast B of round 0
-      double a, b;
-      rig_candidates(P, nullptr, nullptr, false, s_ctl.cur, s_ctl.cur, a, b);
-    }
-    __syncthreads();
-    bool failed = false;
-    for (int round = 0; round < Q.max_rounds; ++round) {
-      const unsigned e = Q.epoch0 + (unsigned)round + 1u;
-      const bool phase0 = round == 0;
-      // ---- broadcast B(e): what this round's sweep evaluates
-      if (tid == 0) {
-        s_bc[0] = (double)((s_ctl.done ? 1 : 0) | ((phase0 || s_ctl.step_valid) ? 2 : 0) | ((s_ctl.cur & 1) << 3));
-        s_bc[1] = s_ctl.radius;
-      }
-      if (!phase0 && tid < S) s_bc[2 + tid] = -smem[(size_t)S * ((S + 1) | 1) + tid];   // the shared step: -x of rig_solve_block (s_b)
-      if (phase0 && tid < S) s_bc[2 + tid] = 0.0;
-      for (int i = tid; i < 32 * C; i += 256) s_bc[2 + S + i] = P.camrec[i];
-      __syncthreads();
-      for (int w = tid; w < 2 * NB; w += 256) ag_st(Q.ybox + w, granule(e, s_bc[w >> 1], w & 1));
-      if (s_ctl.done) break;
-      // ---- statistics rows -> decision
-      const bool swept = phase0 || s_ctl.step_valid;
-      {
-        const int nst = phase0 ? KS : 4;
-        for (int c0 = 0; c0 < nst; c0 += 8) {
-          if (tid < 8) s_cols[tid] = c0 + tid;
-          __syncthreads();
-          double out8[8];
-          const int nc = nst - c0 < 8 ? nst - c0 : 8;
-          if (!rig_gather_cols<8>(Q.sbox, G, KS, s_cols, nc, -1, e, s4, out8, fail, Q.timeout_shift)) failed = true;
-          if (tid == 0) {
+      const int nst = phase0 ? KS : 4;
+      for (int c0 = 0; c0 < nst; c0 += 8) {
+        if (tid < 8) s_cols[tid] = c0 + tid;
+        __syncthreads();
+        double out8[8];
+        const int nc = nst - c0 < 8 ? nst - c0 : 8;
+        if (!rig_gather_cols<8>(Q.sbox, G, KS, s_cols, nc, -1, e, s4, out8, fail, Q.timeout_shift)) failed = true;
+        if (tid == 0) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if (j < nc) s_tot[c0 + j] = out8[j];
-          }
-          __syncthreads();
+          for (int j = 0; j < 8; ++j)
+            if (j < nc) s_tot[c0 + j] = out8[j];
         }
+        __syncthreads();
       }
-      if (failed) break;
-      // |x|^2 of the shared block at the starting point (k_rig_init)
-      double x2_shared = 0.0;
+    }
+    if (failed) break;
+    // |x|^2 of the shared block at the starting point (k_rig_init)
+    double x2_shared = 0.0;
+    if (phase0) {
+      double x2 = 0.0;
+      const int cur0 = s_ctl.cur;
+      for (int i = tid; i < C * 7; i += 256) {
+        const int cc2 = i / 7;
+        const double v = P.cam[((size_t)cur0 * C + cc2) * 8 + (i - cc2 * 7)];
+        x2 += P.cam_fixed[cc2] ? 0.0 : v * v;
+      }
+      x2_shared = block_sum256(x2, s4);
+    }
+    if (tid == 0) {
+      LmCtl c = s_ctl;
+      const LmOpts o = *P.opts;
+      const int prev_cur = c.cur & 1, was_valid = c.step_valid;
+      const double prev_radius = c.radius;
+      s_has_rec = 0;
       if (phase0) {
-        double x2 = 0.0;
-        const int cur0 = s_ctl.cur;
-        for (int i = tid; i < C * 7; i += 256) {
-          const int cc2 = i / 7;
-          const double v = P.cam[((size_t)cur0 * C + cc2) * 8 + (i - cc2 * 7)];
-          x2 += P.cam_fixed[cc2] ? 0.0 : v * v;
-        }
-        x2_shared = block_sum256(x2, s4);
+        for (int k = 0; k < S; ++k) s_ss[k] = o.jacobi_scaling ? 1.0 / (1.0 + sqrt(s_tot[4 + k])) : 1.0;
+        lm_init(c, o, s_tot[0], sqrt(s_tot[3] + x2_shared));
+      } else if (c.cand_pending) {
+        double step2 = swept ? s_tot[2] : 0.0, xn2 = swept ? s_tot[3] : 0.0;
+        if (c.step_valid) { step2 += P.shared_stats[0]; xn2 += P.shared_stats[1]; }
+        const int len0 = c.log_len;
+        lm_decide(c, o, &s_rec, swept ? s_tot[0] : 0.0, swept ? s_tot[1] : 0.0, step2, xn2);
+        s_has_rec = (c.log_len != len0 && c.log_len <= P.log_cap) ? 1 : 0;
+        if (s_has_rec) P.log[c.log_len - 1] = s_rec;
       }
-      if (tid == 0) {
-        LmCtl c = s_ctl;
-        const LmOpts o = *P.opts;
-        const int prev_cur = c.cur & 1, was_valid = c.step_valid;
-        const double prev_radius = c.radius;
-        s_has_rec = 0;
-        if (phase0) {
-          for (int k = 0; k < S; ++k) s_ss[k] = o.jacobi_scaling ? 1.0 / (1.0 + sqrt(s_tot[4 + k])) : 1.0;
-          lm_init(c, o, s_tot[0], sqrt(s_tot[3] + x2_shared));
-        } else if (c.cand_pending) {
-          double step2 = swept ? s_tot[2] : 0.0, xn2 = swept ? s_tot[3] : 0.0;
-          if (c.step_valid) { step2 += P.shared_stats[0]; xn2 += P.shared_stats[1]; }
-          const int len0 = c.log_len;
-          lm_decide(c, o, &s_rec, swept ? s_tot[0] : 0.0, swept ? s_tot[1] : 0.0, step2, xn2);
-          s_has_rec = (c.log_len != len0 && c.log_len <= P.log_cap) ? 1 : 0;
-          if (s_has_rec) P.log[c.log_len - 1] = s_rec;
-        }
-        if (!c.done && round + 1 >= Q.max_rounds) { c.done = 1; c.term = CC_NO_CONVERGENCE; }
-        s_ctl = c;
-        // did the workers' assumption hold? (the expression they evaluate: persist_spec_radius)
-        s_hit = Q.pbox != nullptr && !phase0 && swept && was_valid && !c.done && (c.cur & 1) == (prev_cur ^ 1) &&
-                c.radius == persist_spec_radius(prev_radius, o.max_radius);
-        s_a[0] = (double)((c.done ? 1 : 0) | (s_hit ? 4 : 0) | ((c.cur & 1) << 3));
-        s_a[1] = c.radius;
-      }
-      __syncthreads();
-      if (tid < S) { s_a[2 + tid] = phase0 ? s_ss[tid] : 0.0; if (phase0) P.ss[tid] = s_ss[tid]; }
-      __syncthreads();
-      for (int w = tid; w < 2 * (2 + S); w += 256) ag_st(Q.abox + w, granule(e, s_a[w >> 1], w & 1));
-      if (s_ctl.done) {
-        if (tid == 0) { *P.ctl = s_ctl; *P.ctl_next = s_ctl; }
-        break;
-      }
-      // ---- the K column sums -> the layout rig_solve_block reads (P.vec), then the solve step
-      if (tid == 0) s_flag = 0;
-      __syncthreads();
-      {
-        const long long t0 = wall_clock64();
-        bool good = true;
-        for (int k0 = tid; k0 < K && good; k0 += 256 * 4) {
-          u64 lo[4], hi[4];
-          for (unsigned spins = 0;; ++spins) {
-            bool ok = true;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int k = k0 + 256 * u;
-              const u64* p = (s_hit ? Q.pcbox : Q.cbox) + (size_t)(k < K ? k : k0) * 2;
-              lo[u] = ag_ld(p);
-              hi[u] = ag_ld(p + 1);
-              ok = ok && (unsigned)(lo[u] >> 32) == e && (unsigned)(hi[u] >> 32) == e;
-            }
-            if (ok) break;
-            if ((spins & 63u) == 63u && (timed_out(t0, Q.timeout_shift) || ag_ld32(fail) != 0u)) { good = false; break; }
-            __builtin_amdgcn_s_sleep(1);
-          }
-          if (!good) break;
+      if (!c.done && round + 1 >= Q.max_rounds) { c.done = 1; c.term = CC_NO_CONVERGENCE; }
+      s_ctl = c;
+      // did the workers' assumption hold? (the expression they evaluate: persist_spec_radius)
+      // (Q.pbox is never null. The test stays: without it this kernel's register allocation moves, 309 / 53 vector /
+      // accumulation registers for 308 / 52, and a moved allocation has cost this path 25 us a launch before.)
+      s_hit = Q.pbox != nullptr && !phase0 && swept && was_valid && !c.done && (c.cur & 1) == (prev_cur ^ 1) &&
+              c.radius == persist_spec_radius(prev_radius, o.max_radius);
+      s_a[0] = (double)((c.done ? 1 : 0) | (s_hit ? 4 : 0) | ((c.cur & 1) << 3));
+      s_a[1] = c.radius;
+    }
+    __syncthreads();
+    if (tid < S) { s_a[2 + tid] = phase0 ? s_ss[tid] : 0.0; if (phase0) P.ss[tid] = s_ss[tid]; }
+    __syncthreads();
+    for (int w = tid; w < 2 * (2 + S); w += 256) ag_st(Q.abox + w, granule(e, s_a[w >> 1], w & 1));
+    if (s_ctl.done) {
+      if (tid == 0) { *P.ctl = s_ctl; *P.ctl_next = s_ctl; }
+      break;
+    }
+    // ---- the K column sums -> the layout rig_solve_block reads (P.vec), then the solve step
+    if (tid == 0) s_flag = 0;
+    __syncthreads();
+    {
+      const long long t0 = wall_clock64();
+      bool good = true;
+      for (int k0 = tid; k0 < K && good; k0 += 256 * 4) {
+        u64 lo[4], hi[4];
+        for (unsigned spins = 0;; ++spins) {
+          bool ok = true;
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int k = k0 + 256 * u;
-            if (k < K) {
-              const double v = ungranule(lo[u], hi[u]);
-              if (k == K - 1) vl[P.PC + P.rank] = v;   // the gradient maximum rides in the rank's slot (k_rig_reduce)
-              else vl[Q.comp[k]] = v;
-            }
+            const u64* p = (s_hit ? Q.pcbox : Q.cbox) + (size_t)(k < K ? k : k0) * 2;
+            lo[u] = ag_ld(p);
+            hi[u] = ag_ld(p + 1);
+            ok = ok && (unsigned)(lo[u] >> 32) == e && (unsigned)(hi[u] >> 32) == e;
+          }
+          if (ok) break;
+          if ((spins & 63u) == 63u && (timed_out(t0, Q.timeout_shift) || ag_ld32(fail) != 0u)) { good = false; break; }
+          __builtin_amdgcn_s_sleep(1);
+        }
+        if (!good) break;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int k = k0 + 256 * u;
+          if (k < K) {
+            const double v = ungranule(lo[u], hi[u]);
+            if (k == K - 1) vl[P.PC + P.rank] = v;   // the gradient maximum rides in the rank's slot (k_rig_reduce)
+            else vl[Q.comp[k]] = v;
           }
         }
-        if (!good) s_flag = 1;
       }
-      __syncthreads();
-      if (s_flag == 1) { failed = true; break; }
-      if (tid == 0) { *P.ctl = s_ctl; *P.ctl_next = s_ctl; }   // (rig_solve_block finishes the record of this round in P.log)
-      __syncthreads();
-      rig_solve_block<3>(Pc, smem, &s_ctl, vl);
-      __syncthreads();
-      if (tid == 0) s_ctl = *P.ctl;   // as the solve step left it (this workgroup wrote it)
-      __syncthreads();
+      if (!good) s_flag = 1;
     }
-    // ---- the solve is over
     __syncthreads();
-    if (tid == 0) {
-      LmCtl c = s_ctl;
-      if (failed || ag_ld32(fail) != 0u) {
-        __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        c.done = 1; c.term = CC_FAILURE_EXCHANGE;
-      }
-      if (!c.done) { c.done = 1; c.term = CC_NO_CONVERGENCE; }
-      *P.ctl = c;
-      *P.ctl_next = c;
-      rig_publish(P, c);
+    if (s_flag == 1) { failed = true; break; }
+    if (tid == 0) { *P.ctl = s_ctl; *P.ctl_next = s_ctl; }   // (rig_solve_block finishes the record of this round in P.log)
+    __syncthreads();
+    rig_solve_block<3>(Pc, smem, &s_ctl, vl);
+    __syncthreads();
+    if (tid == 0) s_ctl = *P.ctl;   // as the solve step left it (this workgroup wrote it)
+    __syncthreads();
+  }
+  // ---- the solve is over
+  __syncthreads();
+  if (tid == 0) {
+    LmCtl c = s_ctl;
+    if (failed || ag_ld32(fail) != 0u) {
+      __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      c.done = 1; c.term = CC_FAILURE_EXCHANGE;
     }
+    if (!c.done) { c.done = 1; c.term = CC_NO_CONVERGENCE; }
+    *P.ctl = c;
+    *P.ctl_next = c;
+    rig_publish(P, c);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
-// The LEAN workers of the persistent rig solve (k_rig_persist_w; small rigs: at most 4 observed cameras, 24 shared
-// coordinates) with the control workgroup as a launch of its own beside them (k_rig_persist_ctl: rig_persist_control, on a
-// second stream -- it needs 230 registers a thread, the workers must stay under 128 to put SIXTEEN waves on a compute
-// unit). Same seams, same rows, same control as k_rig_persist; what differs is where a worker keeps its four frames:
-// in LDS -- poses, frame records, the 16 x 16 blocks and compact records of their groups (both buffers), Y, the Jacobi
-// scales -- and how it works on them: one WAVE PER GROUP in the sweep (sixteen at once; k_rig_persist: four, one after
-// the other), sixteen lanes per frame in the pose update, one wave per frame in the elimination, which builds the
-// compact row straight from a slot table (cc_intrinsics_persist.hip's way) instead of going through the partial-row layout.
+// The workers (k_rig_persist_w; small rigs: at most 4 observed cameras, 24 shared coordinates). The control is a launch of
+// its own beside them (k_rig_persist_ctl, on a second stream) because it needs 230 registers a thread and the workers must
+// stay under 128 to put SIXTEEN waves on a compute unit. The capacities and the LDS layout of a worker:
 // ---------------------------------------------------------------------------------------------
 constexpr int kRpwMaxS = 24;        // shared coordinates: four optimised cameras (none of them frozen)
 constexpr int kRpwMaxCO = 4;        // observed cameras = groups of a frame = sweep waves of a team
@@ -469,7 +467,7 @@ __global__ __launch_bounds__(TEAMS * 256) void k_rig_persist_w(RigDev P, RigPers
   int* s_good = s_cols + 8;
   // ---- every worker is RESIDENT once all G have passed this point: the last one tells the host, which launches the control
   // only then -- its candidates therefore only ever run on compute units the workers left free (k_rig_persist_ctl)
-  if (Q.gate && tid0 == 0) {
+  if (Q.gate && tid0 == 0) {   // (never null; the test stays: without it the workers' instructions differ from the measured ones)
     const unsigned prev = __hip_atomic_fetch_add(P.arrive + 13, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (prev + 1u == (unsigned)G) __hip_atomic_store(Q.gate, (unsigned long long)(Q.epoch0 + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }

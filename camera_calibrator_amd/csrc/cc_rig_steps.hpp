@@ -5,8 +5,10 @@
 
 // ---------------------------------------------------------------------------------------------
 // update: per frame, back-substitute the pose step and form the candidate pose. 16 lanes/frame, 16 frames per
-// 256-thread block (`fblk` = which sixteen). SC1: the shared step `ds` was written by another workgroup of the
-// SAME launch (fused into k_rig_reduce): read it with sc1 loads.
+// 256-thread block. Two forms: k_rig_update, a launch of its own (SC1 = PRE = false: plain loads), and the fused tail of
+// k_rig_reduce (SC1: the shared step P.ds was written by another workgroup of the SAME launch, read it with sc1 loads;
+// PRE: everything else was fetched ahead of the solving block's flag, rig_update_prefetch). The lean persistent workers
+// have a pose update of their own (k_rig_persist_w: the frame's state lives in LDS).
 // ---------------------------------------------------------------------------------------------
 // What the update of a frame needs besides the shared step: fetched by the blocks of k_rig_reduce WHILE they wait for
 // the solving block's flag (SW <= 32: two Y columns per lane), so that only the step itself is read behind the flag.
@@ -38,12 +40,10 @@ __device__ __forceinline__ void rig_update_prefetch(const RigDev& P, int64_t f, 
 }
 
 template <bool SC1, bool PRE = false>
-// f: frame of this thread's sixteen lanes; ds_lds: the shared step in LDS (persistent kernel), else read from P.ds
-__device__ __forceinline__ void rig_update_body(const RigDev& P, int phase, int cur, int64_t f, const RigUpdPre& pre, const double* ds_lds = nullptr) {
+// f: frame of this thread's sixteen lanes
+__device__ __forceinline__ void rig_update_body(const RigDev& P, int phase, int cur, int64_t f, const RigUpdPre& pre) {
   const int dst = phase == 0 ? cur : (cur ^ 1);
-  int tid_ = threadIdx.x;
-  if (ds_lds) asm volatile("" : "+v"(tid_));
-  const int tid = tid_, l = tid & 15;
+  const int tid = threadIdx.x, l = tid & 15;
   const bool valid = f < P.F;
   const int64_t fc = valid ? f : 0;
   double u[6] = {0, 0, 0, 0, 0, 0};
@@ -66,13 +66,6 @@ __device__ __forceinline__ void rig_update_body(const RigDev& P, int phase, int 
     // issued before the first product (round 6; the rolled loop waited for each column's seven loads on their own: eight
     // dependent round trips behind the flag at S = 114, 14 us of the reduce launch). Same products in the same order.
     const double* Yf = P.Y + (size_t)fc * 6 * P.SW;
-    if (ds_lds) {   // (the lean persistent workers: at most 25 columns, a register budget of their own -- the plain loop)
-      for (int k = l; k < P.SW; k += 16) {
-        const double d = k < P.S ? ds_lds[k] : 1.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) u[i] += Yf[i * P.SW + k] * d;
-      }
-    } else
     for (int k0 = l; k0 < P.SW; k0 += 128) {
       double y[8][6], d[8];
 #pragma unroll
@@ -435,14 +428,12 @@ __global__ __launch_bounds__(256) void k_rig_init(RigDev P) {
 // ---------------------------------------------------------------------------------------------
 // NR = direct-sum accumulators per lane: 8 covers ND <= 512 (the usual rigs: <= 18 observed cameras with poses only, 3 with
 // intrinsics), 24 the full range; the small variant exists because the kernel sits at the register limit.
-// The elimination as a function: k_rig_elim (a launch of its own: trust-region decision, then the elimination) and the
-// persistent per-solve kernel (PS: the decision is the control workgroup's -- which buffer holds the point to eliminate,
-// the radius, whether this is the first elimination, and the Jacobi scales of the shared columns come as arguments).
 // FM: the sweep was k_rig_sweep_frame -- a group's record is [G7 (28) | T (36)] (P.gcomp), the frame block comes summed (P.fsum).
 // KC: the sweep was k_rig_sweep_k2 (intrinsics, compact records of kRigRecK doubles in P.gcomp: offsets kRk*).
-template <bool HK, int NR, bool PS, bool FM = false, bool KC = false>
-__device__ __forceinline__ void rig_elim_body(const RigDev& P, char* smem_raw, const int ps_cur, const double ps_radius, const bool ps_first,
-                                              const double* ps_ss) {
+// (The body is a function of its own: written into k_rig_elim itself it is optimised in another order -- not on its own, through
+// the reference, before it is inlined -- and all eight variants come out with other instructions; measured once, left alone.)
+template <bool HK, int NR, bool FM, bool KC>
+__device__ __forceinline__ void rig_elim_body(const RigDev& P, char* smem_raw) {
   static_assert(!(HK && FM), "the frame form is the poses-only sweep's");
   static_assert(!KC || HK, "compact K records belong to the sweep with intrinsics");
   double* s_Z = reinterpret_cast<double*>(smem_raw);         // [24][ZS] staged Z rows of the four frames
@@ -457,23 +448,19 @@ __device__ __forceinline__ void rig_elim_body(const RigDev& P, char* smem_raw, c
   __shared__ double s_tot[4];
   __shared__ double s_fg[8];
   __shared__ LmCtl s_ctl;
-  int tid_ = threadIdx.x;
-  if (PS) asm volatile("" : "+v"(tid_));   // (a fresh copy per call: the lane tables below are rebuilt every round of the persistent kernel instead of
-                                              //  being hoisted out of its round loop and kept -- spilled -- across the sweep)
-  const int tid = tid_, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const LmCtl* ctl = P.ctl;
-  const int ctl_done = PS ? 0 : ctl->done, ctl_phase = PS ? 1 : ctl->phase;
+  const int ctl_done = ctl->done, ctl_phase = ctl->phase;
   // what thread 0 needs for the trust-region decision, fetched now instead of behind the statistics barrier
   LmCtl c_in;
   LmOpts o_in;
   double sh0 = 0.0, sh1 = 0.0;
-  if constexpr (!PS) { c_in = *ctl; o_in = *P.opts; sh0 = P.shared_stats[0]; sh1 = P.shared_stats[1]; }
+  c_in = *ctl; o_in = *P.opts; sh0 = P.shared_stats[0]; sh1 = P.shared_stats[1];
   // ... and, frame form, the statistics rows themselves (one per frame: eight per thread up to 2048 frames): requested next
   // to the control block instead of behind it
-  constexpr bool kPre = FM && !PS;
-  d2 pre_g[kPre ? 8 : 1], pre_f[kPre ? 8 : 1];
-  const bool pre = kPre && P.fmode && P.F <= 2048 && !P.comm;
-  if constexpr (kPre) {
+  d2 pre_g[FM ? 8 : 1], pre_f[FM ? 8 : 1];
+  const bool pre = FM && P.fmode && P.F <= 2048 && !P.comm;
+  if constexpr (FM) {
     if (pre) {
       const d2* gs2 = reinterpret_cast<const d2*>(P.gstats);
       const d2* fs2 = reinterpret_cast<const d2*>(P.fstats);
@@ -532,14 +519,12 @@ __device__ __forceinline__ void rig_elim_body(const RigDev& P, char* smem_raw, c
     t_ij[u] = __builtin_amdgcn_readfirstlane((int)P.tile_i[ic] | ((int)P.tile_j[ic] << 8));
   }
   if (ctl_done || ctl_phase == 0) return;
-  bool pending = false;
-  if constexpr (!PS) {
-  pending = ctl->cand_pending != 0;
+  const bool pending = ctl->cand_pending != 0;
   if (P.comm) {
     if (tid < 4) s_tot[tid] = P.vec_stats[tid];
     __syncthreads();
   } else {
-    if (kPre && pre) rig_reduce_stats(P, pending && ctl->step_valid, s16, s_tot, pre_g, pre_f);
+    if (pre) rig_reduce_stats(P, pending && ctl->step_valid, s16, s_tot, pre_g, pre_f);
     else rig_reduce_stats(P, pending && ctl->step_valid, s16, s_tot);
   }
   if (tid == 0) {
@@ -556,15 +541,14 @@ __device__ __forceinline__ void rig_elim_body(const RigDev& P, char* smem_raw, c
     s_ctl = c;
     if (blockIdx.x == 0) *P.ctl_next = c;
   }
-  }   // (!PS)
-  if (tid < P.S) s_ss[tid] = (PS ? ps_ss : P.ss)[tid];
+  if (tid < P.S) s_ss[tid] = P.ss[tid];
   for (int i = tid; i < 24 * P.ZS; i += 256) s_Z[i] = 0.0;   // padding columns stay zero
   __syncthreads();
-  if (!PS && s_ctl.done) return;
-  const int cur = PS ? ps_cur : s_ctl.cur;
-  const double inv_radius = 1.0 / (PS ? ps_radius : s_ctl.radius);
+  if (s_ctl.done) return;
+  const int cur = s_ctl.cur;
+  const double inv_radius = 1.0 / s_ctl.radius;
   const double mn = P.opts->min_lm_diagonal, mx = P.opts->max_lm_diagonal;
-  const bool first_elim = PS ? ps_first : (ctl->phase == 1 && s_ctl.iter == 0 && !pending);   // Jacobi scale of the frame blocks
+  const bool first_elim = ctl->phase == 1 && s_ctl.iter == 0 && !pending;   // Jacobi scale of the frame blocks
   const bool jac = P.opts->jacobi_scaling != 0;
   const int SW = P.SW, S = P.S, ZS = P.ZS;
   const size_t gs = FM ? (size_t)64 : (KC ? (size_t)kRigRecK : (size_t)P.gstride);
@@ -813,7 +797,7 @@ template <bool HK, int NR, bool FM = false, bool KC = false>
 __global__ __launch_bounds__(256) void k_rig_elim(RigDev P) {
   rig_progress(P, RIG_PROG_ELIM);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  rig_elim_body<HK, NR, false, FM, KC>(P, smem_raw, 0, 1.0, false, nullptr);
+  rig_elim_body<HK, NR, FM, KC>(P, smem_raw);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -828,14 +812,6 @@ __global__ __launch_bounds__(256) void k_rig_elim(RigDev P) {
 // Tried and dropped in round 1 (S = 24): a single-wave factorisation through LDS (33 us vs 20) and a
 // register-tiled one with only the pivot column crossing threads through LDS (23 us).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double readlane_d(double x, int l) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-  return __hiloint2double(hi, lo);
-}
-
-
-
 // shared step: write-through, so that workgroups of the same launch can read it behind a flag (sc1 loads)
 __device__ __forceinline__ void store_ds(double* p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -937,7 +913,7 @@ __device__ __forceinline__ void chol_panel(double* A, int S, int LD, int j0, int
   // The pivot of the NEXT column is taken ahead of the column's own update (two lane reads and one FMA, the very
   // operation the update performs on that entry, so the value is the same bit for bit): its reciprocal square root is
   // then computed while the LDS round trip of the multipliers is in flight instead of behind it.
-  double d = (!TWO || j0 < 64) ? readlane_d(p0[0], j0 & 63) : readlane_d(p1[0], j0 & 63);
+  double d = (!TWO || j0 < 64) ? lane_bcast(p0[0], j0 & 63) : lane_bcast(p1[0], j0 & 63);
   double inv = rsqrt_pos(d);
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
@@ -954,8 +930,8 @@ __device__ __forceinline__ void chol_panel(double* A, int S, int LD, int j0, int
       wave_lds_fence();
       if (c + 1 < 8 && c + 1 < nc) {
         const int cn = col + 1;
-        const double ln = (!TWO || cn < 64) ? readlane_d(l0, cn & 63) : readlane_d(l1, cn & 63);          // L[cn][col]
-        const double pn = (!TWO || cn < 64) ? readlane_d(p0[c + 1], cn & 63) : readlane_d(p1[c + 1], cn & 63);
+        const double ln = (!TWO || cn < 64) ? lane_bcast(l0, cn & 63) : lane_bcast(l1, cn & 63);          // L[cn][col]
+        const double pn = (!TWO || cn < 64) ? lane_bcast(p0[c + 1], cn & 63) : lane_bcast(p1[c + 1], cn & 63);
         d = fma(-ln, ln, pn);
         inv = rsqrt_pos(d);
       }
@@ -970,7 +946,7 @@ __device__ __forceinline__ void chol_panel(double* A, int S, int LD, int j0, int
         if (TWO) p1[c2] = fma(-l1, m[c2], p1[c2]);
       }
       // forward substitution: y_col = b_col / L_col,col, b_i -= L_i,col y_col (i > col)
-      const double yj = ((!TWO || col < 64) ? readlane_d(b0, col & 63) : readlane_d(b1, col & 63)) * inv_c;
+      const double yj = ((!TWO || col < 64) ? lane_bcast(b0, col & 63) : lane_bcast(b1, col & 63)) * inv_c;
       b0 = i0 == col ? yj : (i0 > col ? b0 - l0 * yj : b0);
       if (TWO) b1 = i1 == col ? yj : (i1 > col ? b1 - l1 * yj : b1);
       wave_lds_fence();
@@ -1001,14 +977,14 @@ __device__ __forceinline__ void chol_backward(const double* A, int S, int LD, do
         const int j = j0 - u, jr = j >= 64 ? j : 64;
         const double x0 = A[(size_t)jr * LD + i0];
         const double x1 = A[(size_t)jr * LD + (i1 < LD ? i1 : 0)];
-        const double vj = readlane_d(v1, jr - 64);
+        const double vj = lane_bcast(v1, jr - 64);
         a0[u] = j >= 64 ? x0 * vj : 0.0;              // (every row i0 < 64 <= j)
         a1[u] = (j >= 64 && i1 < j) ? x1 * vj : 0.0;
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int jr = j0 - u >= 64 ? j0 - u : 64;   // (steps below row 64 multiply by the zeros selected above)
-        const double bj = readlane_d(b1, jr - 64);
+        const double bj = lane_bcast(b1, jr - 64);
         b0 -= a0[u] * bj;
         b1 -= a1[u] * bj;
       }
@@ -1022,13 +998,13 @@ __device__ __forceinline__ void chol_backward(const double* A, int S, int LD, do
       const int j = j0 - u, jr = j >= 0 ? j : 0;
       // (unconditional loads from row jr, then a select: a conditional load is a branch and a wait of its own)
       const double x0 = A[(size_t)jr * LD + i0];
-      const double vj = readlane_d(v0, jr);
+      const double vj = lane_bcast(v0, jr);
       a0[u] = (j >= 0 && i0 < j) ? x0 * vj : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int jr = j0 - u >= 0 ? j0 - u : 0;   // (steps below row 0 multiply by the zeros selected above)
-      const double bj = readlane_d(b0, jr);      // final: rows > j are done
+      const double bj = lane_bcast(b0, jr);      // final: rows > j are done
       b0 -= a0[u] * bj;
     }
   }
@@ -1165,14 +1141,14 @@ __device__ __forceinline__ bool chol_block4(double* A, int S, int LD, double* s_
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         if (c < nb) {   // (uniform)
-          const double d = readlane_d(x[c], j0 + c);
+          const double d = lane_bcast(x[c], j0 + c);
           ok = ok && (d > 0.0) && isfinite(d);
           const double inv = rsqrt_pos(d);
           const double y = x[c] * inv;            // lane j0 + c: d * inv = L_cc; lanes above it: not part of the column
           x[c] = y;
           if (ln == j0 + c) s_inv[j0 + c] = inv;
 #pragma unroll
-          for (int c2 = c + 1; c2 < 4; ++c2) x[c2] = fma(-y, readlane_d(y, (j0 + c2) & 63), x[c2]);
+          for (int c2 = c + 1; c2 < 4; ++c2) x[c2] = fma(-y, lane_bcast(y, (j0 + c2) & 63), x[c2]);
         }
       }
       if (ln <= S) {

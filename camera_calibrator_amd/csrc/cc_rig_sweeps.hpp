@@ -96,13 +96,13 @@ __device__ __forceinline__ void reduce_scatter32(double* p, int lane) {
 }
 
 constexpr int kRigAdjWaves = 4;    // waves per SIMD the one-wave-per-group sweep is compiled for (128 registers)
-// The sweep of one group as a function: k_rig_sweep_adj (one workgroup per group) and the persistent per-solve kernel
-// (k_rig_persist: WL -- "wave-local": the caller is ONE wave of a larger workgroup sweeping the groups of its frame one
-// after the other, so there is no workgroup barrier in here, the scratch `lds` is the wave's own, and the camera records
-// come from `camrec` -- there: the copy the control workgroup broadcast, in LDS).
+// The sweep of one group as a function: k_rig_sweep_adj (one workgroup of NW waves per group) and the lean persistent
+// workers (k_rig_persist_w: NW = 1, WL -- "wave-local": the caller is ONE wave of a larger workgroup, each of whose waves
+// sweeps a group of its own, so there is no workgroup barrier in here, the scratch `lds` is the wave's own, and the camera
+// records come from `camrec` -- there: the copy the control workgroup broadcast, in LDS).
 constexpr int kRigSweepAdjLds(int NW) { return 64 + 64 + 8 + NW * 32 + 32 + 36; }   // doubles of scratch
-// where a group's sweep reads and leaves things: global memory (the stand-alone kernels, k_rig_persist) or the LDS of a
-// workgroup that keeps its frames resident (k_rig_persist_w)
+// where a group's sweep reads and leaves things: global memory (the stand-alone kernels) or the LDS of a workgroup that
+// keeps its frames resident (k_rig_persist_w)
 struct RigSweepIO {
   const double* camrec;     // [C][32] camera records of the point to evaluate
   const double* frec;       // [32]    record of the group's frame
@@ -127,7 +127,7 @@ __device__ __forceinline__ void rig_sweep_adj_body(const RigDev& P, const int64_
   double* s_m = s_g + 32;              // [36] M
   auto sync = [] { if (WL) wave_lds_fence(); else __syncthreads(); };
   int tid_ = WL ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
-  if (WL) asm volatile("" : "+v"(tid_));   // (a fresh copy per call: nothing derived from it is hoisted out of the persistent kernel's round loop)
+  if (WL) asm volatile("" : "+v"(tid_));   // (a fresh copy per call: nothing derived from it is hoisted out of the lean workers' round loop)
   const int tid = tid_, lane = tid & 63, wave = tid >> 6;
   const int c = P.gcam[g];
   const int64_t s0 = P.goff[g], s1 = P.goff[g + 1];

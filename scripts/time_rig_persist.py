@@ -1,5 +1,6 @@
-"""Where a round of the persistent rig kernels goes (default: the lean form; CC_RIG_PERSIST=1 CC_RIG_PERSIST_LEAN=0: the glued one) (timing-only build -DCC_RIG_PTIMING: wall-clock marks of worker 0 and of
-the control workgroup in round 3, left in vec_stats). One JSON line."""
+"""Where a round of the lean persistent rig kernels (k_rig_persist_w + k_rig_persist_ctl) goes: wall-clock marks of worker 0 and of
+the control workgroup in round 3, left in vec_stats by the timing-only build
+(scripts/build_variant.sh rptime cc_rig.hip --patch timing -DCC_RIG_PTIMING, loaded through CC_LIB_PATH). One JSON line."""
 import ctypes as C, json, os, sys
 sys.path.insert(0, ".")
 import numpy as np
