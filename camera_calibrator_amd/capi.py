@@ -87,6 +87,8 @@ EXPORTED_SYMBOLS = [
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
     "cc_rigk_get_camera_intrinsics", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
+    "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
+    "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
 ]
 # every symbol include/cc_harness.h declares (synthetic-input harness, host code)
 HARNESS_SYMBOLS = [
@@ -356,6 +358,134 @@ def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, 
                                         C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
                                         _p(t, C.c_double), C.byref(s)))
     return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
+
+
+def _batch_layout(problems):
+    """problems: one (frame_offsets, uv, xyz) per problem -> (problem_offsets [B+1], frame_offsets [Ftot+1], uv, xyz) of
+    the concatenated batch, as cc_intrinsics_batch_* take it."""
+    poff, foff, uvs, xyzs = [0], [0], [], []
+    for off, uv, xyz in problems:
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        uv, xyz = _f32(uv).reshape(-1, 2), _f32(xyz).reshape(-1, 3)
+        assert off[0] == 0 and len(uv) == off[-1] and len(xyz) == off[-1]
+        foff.extend((off[1:] + foff[-1]).tolist())
+        poff.append(poff[-1] + len(off) - 1)
+        uvs.append(uv)
+        xyzs.append(xyz)
+    uv = np.ascontiguousarray(np.concatenate(uvs), dtype=np.float32) if uvs else np.zeros((0, 2), np.float32)
+    xyz = np.ascontiguousarray(np.concatenate(xyzs), dtype=np.float32) if xyzs else np.zeros((0, 3), np.float32)
+    return np.array(poff, dtype=np.int64), np.array(foff, dtype=np.int64), uv, xyz
+
+
+def _batch_summaries(B, log_capacity):
+    logs = [(Iteration * max(1, log_capacity))() for _ in range(B)]
+    ss = (Summary * B)()
+    for p in range(B):
+        ss[p].log = C.cast(logs[p], C.POINTER(Iteration))
+        ss[p].log_capacity = log_capacity
+    return ss, logs
+
+
+class IntrinsicsBatch:
+    """Handle on a batch of independent single-camera problems resident in HBM (cc_intrinsics_batch_*, an extension:
+    the reference calibrates its cameras one after another). problems: one (frame_offsets, uv, xyz) per problem."""
+
+    def __init__(self, problems, device=0):
+        self._h = C.c_void_p()
+        self.problem_offsets, self.frame_offsets, uv, xyz = _batch_layout(problems)
+        self.n_problems = len(self.problem_offsets) - 1
+        self.n_frames = int(self.problem_offsets[-1])
+        _check(lib().cc_intrinsics_batch_create(C.c_int32(device), C.c_int64(self.n_problems), _p(self.problem_offsets, C.c_int64),
+                                                _p(self.frame_offsets, C.c_int64), _p(uv, C.c_float), _p(xyz, C.c_float),
+                                                C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().cc_intrinsics_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _split(self, a, width):
+        a = a.reshape(-1, width)
+        return [a[self.problem_offsets[p]:self.problem_offsets[p + 1]].copy() for p in range(self.n_problems)]
+
+    def set_state(self, intr, q, t, const_mask=None):
+        """intr: [B][9]; q, t: one array per problem ([F_p][4], [F_p][3]) or the concatenation; const_mask: one per problem."""
+        intr = _f64(np.asarray(intr, dtype=np.float64).reshape(-1))
+        q = _f64(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 4) for x in q]) if isinstance(q, (list, tuple)) else q)
+        t = _f64(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in t]) if isinstance(t, (list, tuple)) else t)
+        assert intr.size == 9 * self.n_problems and q.size == 4 * self.n_frames and t.size == 3 * self.n_frames
+        mask = np.zeros(self.n_problems, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
+        assert mask.size == self.n_problems
+        _check(lib().cc_intrinsics_batch_set_state(self._h, _p(intr, C.c_double), _p(mask, C.c_uint32), _p(q, C.c_double),
+                                                   _p(t, C.c_double)))
+
+    def get_state(self):
+        """(intr [B][9], [q_p], [t_p]): the current point of every problem."""
+        intr = np.zeros((self.n_problems, 9))
+        q = np.zeros((self.n_frames, 4))
+        t = np.zeros((self.n_frames, 3))
+        _check(lib().cc_intrinsics_batch_get_state(self._h, _p(intr, C.c_double), _p(q, C.c_double), _p(t, C.c_double)))
+        return intr, self._split(q, 4), self._split(t, 3)
+
+    def solve(self, options=None, log_capacity=1024):
+        """One summary dictionary per problem (as IntrinsicsProblem.solve returns)."""
+        opt = options if options is not None else default_options()
+        ss, logs = _batch_summaries(self.n_problems, log_capacity)
+        _check(lib().cc_intrinsics_batch_solve(self._h, C.byref(opt), ss))
+        return [_summary_dict(ss[p], logs[p]) for p in range(self.n_problems)]
+
+    def solve_lean(self, options):
+        """cc_intrinsics_batch_solve without logs or Python summaries (timing loops). Returns the iteration counts."""
+        ss = getattr(self, "_lean", None)
+        if ss is None:
+            ss = self._lean = (Summary * self.n_problems)()
+        _check(lib().cc_intrinsics_batch_solve(self._h, C.byref(options), ss))
+        return [ss[p].iterations for p in range(self.n_problems)]
+
+
+def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=None, device=0, log_capacity=1024):
+    """One-shot cc_intrinsics_batch_optimize. problems: one (frame_offsets, uv, xyz) per problem; intr [B][9]; q, t: one array
+    per problem. Returns (intr [B][9], [q_p], [t_p], [summary_p])."""
+    poff, foff, uv, xyz = _batch_layout(problems)
+    B = len(poff) - 1
+    intr = _f64(np.asarray(intr, dtype=np.float64).reshape(-1)).copy()
+    q = _f64(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 4) for x in q])).copy()
+    t = _f64(np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in t])).copy()
+    mask = np.zeros(B, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
+    opt = options if options is not None else default_options()
+    ss, logs = _batch_summaries(B, log_capacity)
+    _check(lib().cc_intrinsics_batch_optimize(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                              _p(uv, C.c_float), _p(xyz, C.c_float), _p(intr, C.c_double), _p(mask, C.c_uint32),
+                                              _p(q, C.c_double), _p(t, C.c_double), ss))
+    qs = [q[poff[p]:poff[p + 1]].copy() for p in range(B)]
+    ts = [t[poff[p]:poff[p + 1]].copy() for p in range(B)]
+    return intr.reshape(B, 9), qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]
+
+
+def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024):
+    """cc_intrinsics_batch_estimate (Zhang initialisation per problem + the batched solve). distortion5: [B][5] or None;
+    const_mask: one per problem or None. Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
+    poff, foff, uv, xyz = _batch_layout(problems)
+    B, F = len(poff) - 1, int(poff[-1])
+    K = np.zeros((B, 9), dtype=np.float32)
+    intr, q, t = np.zeros((B, 9)), np.zeros((F, 4)), np.zeros((F, 3))
+    d5 = _f64(np.asarray(distortion5, dtype=np.float64).reshape(B, 5)) if distortion5 is not None else None
+    mask = np.zeros(B, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
+    opt = options if options is not None else default_options()
+    ss, logs = _batch_summaries(B, log_capacity)
+    _check(lib().cc_intrinsics_batch_estimate(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                              _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                              _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                              _p(t, C.c_double), ss))
+    qs = [q[poff[p]:poff[p + 1]].copy() for p in range(B)]
+    ts = [t[poff[p]:poff[p + 1]].copy() for p in range(B)]
+    return K.reshape(B, 3, 3), intr, qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]
 
 
 HUBER_A = float(np.float32(3.0) / np.float32(500.0))  # extrinsics_calibrator.cpp:176

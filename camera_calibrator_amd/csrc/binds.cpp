@@ -157,6 +157,9 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("LastSolverNote", &Calibrator::LastSolverNote)
       .def("LastFinalCost", &Calibrator::LastFinalCost);
 
+  // extension: several cameras' Estimate() in one call, their bundle adjustments batched on the GPU
+  m.def("EstimateMany", &Calibrator::EstimateMany, py::arg("calibrators"), py::arg("img_points"), py::arg("world_points"));
+
   py::class_<ExtrinsicsCalibrator>(m, "ExtrinsicsCalibrator")
       .def(py::init<>())
       .def("AddCameraTRig", &ExtrinsicsCalibrator::AddCameraTRig, py::arg("camera_T_rig"), py::arg("freeze") = false)

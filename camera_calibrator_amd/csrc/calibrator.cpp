@@ -167,6 +167,86 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
   Optimize(pixels_per_view, board_points_per_view, qs, ts);
 }
 
+// EXTENSION (the reference calibrates its cameras one after another, system_calibration.py / cam_calibration.py:290-314): Estimate()
+// for several calibrators in ONE library call -- cc_intrinsics_batch_estimate runs Zhang's initialisation per camera and then every
+// camera's bundle adjustment together, two launches per LM iteration for the whole set. Every calibrator brings its own constant set
+// and current distortion and gets K / distortion written back as float32 exactly as Estimate() does, plus its Last* fields. All of
+// them run on the first calibrator's device, in the two-kernel batched form (LastSolverForm() == 0).
+void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                              const std::vector<std::vector<Points3D>>& world_points) {
+  const size_t B = calibrators.size();
+  if (img_points.size() != B || world_points.size() != B)
+    throw std::invalid_argument("Calibrator::EstimateMany: calibrators, img_points and world_points must have the same length");
+  if (B == 0) return;
+  const auto t_call = std::chrono::steady_clock::now();
+  std::vector<int64_t> poff(B + 1, 0), foff(1, 0);
+  size_t n_obs = 0;
+  for (size_t p = 0; p < B; ++p) {
+    if (!calibrators[p]) throw std::invalid_argument("Calibrator::EstimateMany: a calibrator is null");
+    if (img_points[p].size() != world_points[p].size())
+      throw std::invalid_argument("Calibrator::EstimateMany: a camera's img_points and world_points differ in their number of views");
+    for (size_t i = 0; i < img_points[p].size(); ++i) {
+      if (img_points[p][i].size() != world_points[p][i].size())
+        throw std::invalid_argument("Calibrator::EstimateMany: a view's image and world points differ in number");
+      n_obs += img_points[p][i].size();
+      foff.push_back((int64_t)n_obs);
+    }
+    poff[p + 1] = (int64_t)foff.size() - 1;
+  }
+  const size_t F = foff.size() - 1;
+  std::vector<float> uv(2 * n_obs + 2), xyz(3 * n_obs + 3);
+  {
+    size_t f = 0;
+    for (size_t p = 0; p < B; ++p)
+      for (size_t i = 0; i < img_points[p].size(); ++i, ++f) {
+        const size_t k = (size_t)foff[f], m = img_points[p][i].size();
+        if (!m) continue;
+        std::memcpy(uv.data() + 2 * k, img_points[p][i].data(), m * sizeof(Point2D));
+        std::memcpy(xyz.data() + 3 * k, world_points[p][i].data(), m * sizeof(Point3D));
+      }
+  }
+  std::vector<double> dist5(5 * B), intr(kNumIntrinsics * B), qd(4 * F), td(3 * F);
+  std::vector<uint32_t> frozen(B, 0u);
+  std::vector<float> K9(9 * B);
+  for (size_t p = 0; p < B; ++p) {
+    for (int i = 0; i < 5; ++i) dist5[5 * p + i] = calibrators[p]->distortion_(i);
+    for (int idx : calibrators[p]->frozen_intrinsics_)
+      if (idx >= 0 && idx < kNumIntrinsics) frozen[p] |= 1u << idx;
+  }
+  cc_options options;
+  cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
+  std::vector<cc_summary> summaries(B);
+  std::memset(summaries.data(), 0, B * sizeof(cc_summary));
+  const int rc = cc_intrinsics_batch_estimate(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                              dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data());
+  for (size_t p = 0; p < B; ++p) calibrators[p]->last_status_ = rc;
+  // the same contract as Estimate(): environment errors and the Zhang preconditions throw, a solver-level status does not
+  if (rc == CC_ERR_NO_DEVICE || rc == CC_ERR_HIP || rc == CC_ERR_COMM || rc == CC_ERR_BAD_ARGUMENT)
+    throw std::runtime_error(std::string("Calibrator::EstimateMany: ") + cc_last_error());
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+  for (size_t p = 0; p < B; ++p) {
+    Calibrator& c = *calibrators[p];
+    const double* k = intr.data() + kNumIntrinsics * p;
+    c.last_iterations_ = summaries[p].iterations;
+    c.last_final_cost_ = summaries[p].final_cost;
+    c.last_solver_form_ = 0;
+    c.last_solver_reruns_ = 0;
+    c.last_solver_note_.clear();
+    for (double& v : c.last_timing_ms_) v = 0.0;
+    c.last_timing_ms_[6] = ms;
+    for (int r = 0; r < 3; ++r) for (int col = 0; col < 3; ++col) c.camera_matrix_(r, col) = K9[9 * p + r * 3 + col];
+    c.camera_matrix_(0, 0) = static_cast<float>(k[FX]);
+    c.camera_matrix_(1, 1) = static_cast<float>(k[FY]);
+    c.camera_matrix_(0, 2) = static_cast<float>(k[PX]);
+    c.camera_matrix_(1, 2) = static_cast<float>(k[PY]);
+    c.distortion_(0) = static_cast<float>(k[K1]);
+    c.distortion_(1) = static_cast<float>(k[K2]);
+    c.distortion_(2) = static_cast<float>(k[P1]);
+    c.distortion_(3) = static_cast<float>(k[P2]);
+    c.distortion_(4) = static_cast<float>(k[K3]);
+  }
+}
+
 void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const std::vector<Points3D>& board_points_per_view,
                           std::vector<Quaternion>& qs, std::vector<Point3D>& ts) {
   const size_t n_img = pixels_per_view.size();

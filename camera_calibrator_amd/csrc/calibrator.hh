@@ -39,6 +39,15 @@ class Calibrator {
   void Optimize(const std::vector<Points2D>& pixels_per_view, const std::vector<Points3D>& board_points_per_view,
                 std::vector<Quaternion>& qs, std::vector<Point3D>& ts);
 
+  /// EXTENSION (not in the reference): Estimate() for several calibrators in one library call; the cameras' bundle adjustments run
+  /// together on the GPU (cc_intrinsics_batch_estimate: two launches per LM iteration for all of them). calibrators[i] is estimated
+  /// from img_points[i] / world_points[i] with its own constant set and current distortion, and gets K, the distortion and its
+  /// Last* fields exactly as its own Estimate() would set them (results equal to rounding). Runs on calibrators[0]'s device.
+  /// Throws std::invalid_argument when the three lists differ in length (or a camera's two lists, or a view's), and for the
+  /// conditions Estimate() throws for.
+  static void EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                           const std::vector<std::vector<Points3D>>& world_points);
+
   // ---- mapping points through the model ------------------------------------------------------------
   /// pixels -> undistorted normalised coordinates (reference: calibrator.cpp:118-155)
   Points2D Undistort(const Points2D& pixels);

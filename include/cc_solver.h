@@ -256,6 +256,47 @@ int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t ran
 int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]);
 int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks, const uint8_t* handles);
 
+/* ---------------------------------------------------------------------------------------------
+ * EXTENSION (nothing in the reference does it): a BATCH of independent single-camera problems solved together on one
+ * device -- a rig's cameras before the rig solve (system_calibration.py runs optimize_intrinsics camera by camera,
+ * cam_calibration.py:290-314), leave-one-view-out and bootstrap runs, subset fits. Problem p owns frames
+ * [problem_offsets[p], problem_offsets[p+1]) of the concatenated frame list, frame f observations
+ * [frame_offsets[f], frame_offsets[f+1]) of the concatenated uv / xyz. Per LM iteration the WHOLE batch costs two launches
+ * (one sweep workgroup per frame of every problem, one step workgroup per problem); a problem that has finished is left
+ * untouched while the others iterate, and a problem's result -- every bit of state, summary and log -- does not depend on
+ * what else is in the batch or where it sits in it (it differs from cc_intrinsics_solve's in the order of a few sums:
+ * rounding). One device, no exchange, no persistent form.
+ * Bad arguments (n_problems <= 0, a problem without frames, offsets that do not start at 0 or decrease, NULL arrays) are
+ * refused with CC_ERR_BAD_ARGUMENT before any device call.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct cc_intrinsics_batch cc_intrinsics_batch;
+
+int cc_intrinsics_batch_create(int32_t device, int64_t n_problems, const int64_t* problem_offsets /* [B+1] */,
+                               const int64_t* frame_offsets /* [Ftot+1] */, const float* uv, const float* xyz,
+                               cc_intrinsics_batch** out);
+void cc_intrinsics_batch_destroy(cc_intrinsics_batch* h);
+/* intr9 [B][9], const_mask [B] (NULL: nothing held), q_wxyz [Ftot][4], t_xyz [Ftot][3]: the current point of every problem. */
+int cc_intrinsics_batch_set_state(cc_intrinsics_batch* h, const double* intr9, const uint32_t* const_mask,
+                                  const double* q_wxyz, const double* t_xyz);
+int cc_intrinsics_batch_get_state(cc_intrinsics_batch* h, double* intr9, double* q_wxyz, double* t_xyz);
+/* Runs every problem's LM loop from its current point. ONE cc_options for the whole batch; summaries [B] (may be NULL), each
+ * with its own caller-provided log; `seconds` is the wall time of the call in every one. Rounds are enqueued 1 + check_interval
+ * (then check_interval) at a time with plain launches, the B control blocks are read in one transfer after each chunk, and the
+ * call returns when every problem is done. use_graph is IGNORED (nothing is captured); profile_kernels is refused with
+ * CC_ERR_BAD_ARGUMENT; max_iterations above 1023 is clamped to 1023. */
+int cc_intrinsics_batch_solve(cc_intrinsics_batch* h, const cc_options* opt, cc_summary* summaries);
+/* One-shot: create + set_state + solve + get_state + destroy. */
+int cc_intrinsics_batch_optimize(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                 const int64_t* frame_offsets, const float* uv, const float* xyz, double* intr9,
+                                 const uint32_t* const_mask, double* q_wxyz, double* t_xyz, cc_summary* summaries);
+/* cc_intrinsics_estimate for every problem: Zhang's initialisation per problem on the same stream, then the batched solve.
+ * distortion5 [B][5] (NULL: zeros) and const_mask [B] (NULL) are per problem; K_init9 [B][9] (may be NULL) receives Zhang's K.
+ * Every problem needs >= 3 frames with >= 4 points each. */
+int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                 const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                 const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                 cc_summary* summaries);
+
 /* Contiguous frame partition balanced by observation count (host logic, no GPU needed).
  * first_frame has nranks+1 entries; rank r owns frames [first_frame[r], first_frame[r+1]). */
 int cc_partition_frames(int64_t n_frames, const int64_t* frame_offsets, int32_t nranks,
