@@ -378,6 +378,8 @@ __device__ inline double clampd(double v, double lo, double hi) { return fmin(fm
 // the tolerance; this is the same number without the cancellation). For |g_rot| >= 1/4 the block reports the tangent
 // max-norm instead: sin / cos of a "rotation" by 1e6 radians per frame and iteration is not worth a number that is only
 // ever compared with a tolerance of 1e-10 -- every decision is the same for tolerances below 0.14 (oracle: the same rule).
+// A NaN component of g_rot makes n2 NaN, which takes that same branch (`!(n2 < 0.0625)`), and fmax skips the NaN: the block
+// then reports the largest |g_i| of its other five components, a finite number (tests/test_gpu_dev_primitives.py).
 __device__ inline double pose_grad_proj_max(const double* q, const double* g) {
   const double gt = fmax(fmax(fabs(g[3]), fabs(g[4])), fabs(g[5]));
   const double n2 = g[0] * g[0] + g[1] * g[1] + g[2] * g[2];

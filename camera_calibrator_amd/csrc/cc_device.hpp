@@ -42,7 +42,10 @@ __device__ __forceinline__ double wave_sum_mod(double v) {
   return half_pair_sum(row_pair_sum(v));
 }
 __device__ __forceinline__ double wave_sum(double v) { return wave_sum_mod<0>(v); }
-// sum / maximum over the sixteen lanes of a row (lanes 16k .. 16k+15), in every lane
+// sum / maximum over the sixteen lanes of a row (lanes 16k .. 16k+15), in every lane. The maximum has fmax semantics: of
+// all-negative values it is the largest of them (nothing is compared with 0), and a NaN counts as missing -- the other
+// lanes of the row decide, in the NaN's own lane too; only a row of sixteen NaNs gives NaN
+// (tests/test_gpu_dev_primitives.py).
 __device__ __forceinline__ double row16_sum(double v) {
   v += dpp_f64<0xB1>(v);    // quad_perm:[1,0,3,2]
   v += dpp_f64<0x4E>(v);    // quad_perm:[2,3,0,1]

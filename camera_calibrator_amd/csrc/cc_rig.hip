@@ -44,6 +44,7 @@
 #include <mutex>
 #include "cc_device.hpp"
 #include "cc_persist_dev.hpp"
+#include "cc_rig_dev.hpp"
 #include "cc_rig_inner.hpp"
 
 namespace cc {

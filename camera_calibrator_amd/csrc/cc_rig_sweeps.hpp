@@ -17,27 +17,7 @@
 // Rounding differs from the 13-column product by O(eps (|a| / |b|)^2) in the frame-rotation block (a: point relative to
 // the camera pose's origin, b: rotated world point).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void untri(int idx, int& i, int& j) {  // packed lower index -> (i >= j)
-  i = 0;
-  while (tri(i + 1, 0) <= idx) ++i;
-  j = idx - tri(i, 0);
-}
-// 1 / z for the depth of a point in front of the camera (z far from the ends of the exponent range): the hardware
-// estimate and two Newton steps, five instructions instead of the twelve of the IEEE division sequence (scaling, fix-up).
-// Not correctly rounded: within an ulp or two of 1 / z, so the adjoint sweeps (the default) are not bit-identical to
-// the division form that k_rig_obs_cost and the oracle keep (parity is to the stated tolerances under either;
-// the division form is kept as a variant, scripts/variants/exact_arith.patch). Degenerate depths: z = 0 (and z = +-inf) give NaN here (0 * inf inside
-// the first fma) where the division gives +-inf / 0. Both are "not finite" to everything downstream -- the candidate
-// cost fails isfinite() in lm_trial and counts as DBL_MAX, a Gram block holding either fails the Cholesky's
-// `d > 0 && isfinite(d)` test -> invalid step -> the radius shrinks -- so a point that lands on the camera plane is
-// rejected the same way in both forms; a select on the result would cost three instructions per observation of ~165.
-// A point BEHIND the camera (z < 0) is an ordinary finite value in both.
-__device__ __forceinline__ double recip_depth(double z) {
-  double r = __builtin_amdgcn_rcp(z);
-  r = fma(fma(-z, r, 1.0), r, r);
-  r = fma(fma(-z, r, 1.0), r, r);
-  return r;
-}
+// (untri, recip_depth: cc_rig_dev.hpp)
 
 template <int SKIP>
 __device__ __forceinline__ void adj_accumulate(const double* w, double* acc) {
@@ -50,50 +30,7 @@ __device__ __forceinline__ void adj_accumulate(const double* w, double* acc) {
   }
 }
 
-// 32 per-lane values -> their 64-lane sums, value e left in lanes 2e and 2e + 1. Each exchange halves the values a lane
-// carries (31 exchanges and adds instead of 32 x 6), and none of them goes through the LDS crossbar: the two widest
-// are the lane-swap instructions of gfx950 (v_permlane32_swap: lanes 32..63 of the first register <-> lanes 0..31 of the
-// second; v_permlane16_swap: odd 16-lane rows of the first <-> even rows of the second -- after either, first + second
-// is the pairwise sum of the first register's values in the lower lanes / even rows and of the second's in the others),
-// the rest DPP moves inside a row. Partner masks 32, 16, 8, 7 (half-row mirror), 2, 1 are independent, so every value
-// collects all 64 lanes; the lane bit that picks the half kept in each step (5, 4, 3, 2, 1) differs between partners and
-// all earlier ones agree.
-template <int N>
-__device__ __forceinline__ void reduce_swap32(double* p) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const auto l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(p[i]), (unsigned)__double2loint(p[i + N]), false, false);
-    const auto h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(p[i]), (unsigned)__double2hiint(p[i + N]), false, false);
-    p[i] = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-  }
-}
-template <int N>
-__device__ __forceinline__ void reduce_swap16(double* p) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const auto l = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(p[i]), (unsigned)__double2loint(p[i + N]), false, false);
-    const auto h = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(p[i]), (unsigned)__double2hiint(p[i + N]), false, false);
-    p[i] = __hiloint2double((int)h[0], (int)l[0]) + __hiloint2double((int)h[1], (int)l[1]);
-  }
-}
-template <int N, int CTRL, int BIT>
-__device__ __forceinline__ void reduce_dpp(double* p, int lane) {
-  const bool up = (lane & BIT) != 0;
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const double lo = p[i], hi = p[i + N];
-    const double send = up ? lo : hi, keep = up ? hi : lo;
-    p[i] = keep + dpp_f64<CTRL>(send);
-  }
-}
-__device__ __forceinline__ void reduce_scatter32(double* p, int lane) {
-  reduce_swap32<16>(p);
-  reduce_swap16<8>(p);
-  reduce_dpp<4, 0x128, 8>(p, lane);   // row_ror:8
-  reduce_dpp<2, 0x141, 4>(p, lane);   // row_half_mirror
-  reduce_dpp<1, 0x4E, 2>(p, lane);    // quad_perm:[2,3,0,1]
-  p[0] += dpp_f64<0xB1>(p[0]);        // quad_perm:[1,0,3,2]
-}
+// (reduce_swap32 / reduce_swap16 / reduce_dpp / reduce_scatter32: cc_rig_dev.hpp)
 
 constexpr int kRigAdjWaves = 4;    // waves per SIMD the one-wave-per-group sweep is compiled for (128 registers)
 // The sweep of one group as a function: k_rig_sweep_adj (one workgroup of NW waves per group) and the lean persistent
@@ -962,16 +899,7 @@ __device__ __forceinline__ void k2_accumulate(const double* w, double* acc) {
     }
   }
 }
-// 64 per-lane values -> their 64-lane sums, value e in lane e (reduce_scatter32 with one more halving in front and the last
-// step a halving too)
-__device__ __forceinline__ void reduce_scatter64(double* p, int lane) {
-  reduce_swap32<32>(p);
-  reduce_swap16<16>(p);
-  reduce_dpp<8, 0x128, 8>(p, lane);   // row_ror:8
-  reduce_dpp<4, 0x141, 4>(p, lane);   // row_half_mirror
-  reduce_dpp<2, 0x4E, 2>(p, lane);    // quad_perm:[2,3,0,1]
-  reduce_dpp<1, 0xB1, 1>(p, lane);    // quad_perm:[1,0,3,2]
-}
+// (reduce_scatter64: cc_rig_dev.hpp)
 // Weight of entry e of a group's OLD record in the model-cost term q = g^T d + 1/2 d^T H d of the step d = (dc, df, dk): a product
 // of (at most) two step components and 1/2 or 1. The steps lie where the records lie in LDS (sm: camera [12..17], frame
 // [44..49], intrinsics [80..88]); WHICH two, per entry, is a compile-time table (one word per entry: index of the first factor

@@ -247,6 +247,18 @@ def test_reduced_systems_between_65_and_127_coordinates_at_the_edges_of_the_pane
     _assert_same(g, o)
 
 
+@pytest.mark.parametrize("cams", [6, 7, 9, 10, 11])
+def test_reduced_systems_of_30_to_60_coordinates_at_both_ends_of_the_four_column_factorisation(cams):
+    """6 (cams - 1) shared coordinates through chol_block4 (24 < S <= 63, cc_rig_dev.hpp): 6 cameras = 30, the first size
+    after the register-row solve (two 16-row tile rows, a last block of two columns); 7 = 36 and 9 = 48 (three tile rows:
+    48 + the right-hand side's row opens the fourth); 10 = 54 and 11 = 60, the top of the routine for this handle (four tile
+    rows, ten tiles over three waves, the last block full). The oracle on these: FUNCTION tolerance after 4 to 10
+    iterations, one rejected step each. Same bar as every other rig test."""
+    sc = po.rig_scenario(cams, 12, 8)
+    g, o = _both(sc, cams)
+    _assert_same(g, o)
+
+
 def test_rig_kernel_profile_of_a_solve():
     sc = po.rig_scenario(3, 40, 20)
     cq, ct, fq, ft = _inputs(sc)

@@ -237,6 +237,15 @@ def test_rigk_shared_intrinsics_with_more_than_11_observed_cameras_matches_the_o
     _assert_same(g, o)
 
 
+@pytest.mark.parametrize("cams,frames,pts", [(10, 12, 10)])
+def test_rigk_shared_intrinsics_at_63_coordinates_the_last_size_of_the_four_column_factorisation(cams, frames, pts):
+    """10 cameras with one shared intrinsics set: 6 * 9 + 9 = 63 shared coordinates, the last size chol_block4
+    (cc_rig_dev.hpp) takes before the dispatch goes to the one-wave panels -- 63 + the right-hand side's row fill four
+    16-row tile rows exactly (n16 = 4, ten tiles, kMaxT = 4 per wave), the last block has three columns."""
+    g, o = _both(rigk_case(cams, frames, pts))
+    _assert_same(g, o)
+
+
 def test_rigk_per_camera_at_the_largest_supported_size_matches_the_oracle():
     """Seventeen cameras with a camera model of their own: 16 * 6 + 17 * 9 = 249 of at most 255 shared coordinates (reduced
     system in global memory: its packed triangle no longer fits LDS)."""
