@@ -298,11 +298,13 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       asm volatile("" : "+v"(lane));
       const int cur = s_ctl->cur & 1;
       const double radius = s_ctl->radius;
-      double gmax = sv[PC_GMAXP];   // (the maximum over the pose gradients of all ranks)
-#pragma unroll
-      for (int j = 0; j < 9; ++j)
-        if (!(mask & (1u << j))) gmax = fmax(gmax, fabs(sv[PC_GS + j]));
-      const bool go = s_int[0] && !(gmax <= o.gradient_tolerance) && !(radius < o.min_radius);
+      // Ceres' gradient_max_norm, one member per lane: |g_j| of the free shared coordinates on lanes 0..8, the maximum over the pose
+      // gradients (of all ranks) on every other lane and in place of a held coordinate -- a member twice is a member once, and
+      // fmax over the same members gives the same bits in any order (a NaN counts as missing: row16_max). The tree runs behind the
+      // solve, which does not need its result: `go` only decides what becomes of the step.
+      const double gl = (lane < 9 && !((mask >> lane) & 1u)) ? fabs(sv[PC_GS + lane]) : sv[PC_GMAXP];
+      // (what the step is added to and scaled by: read here, in front of the solve, not between the substitutions and the store)
+      const double k_l = s_intr[cur * 16 + (lane < 9 ? lane : 8)], ss_l = s_ss[lane < 9 ? lane : 8];
       bool ok = !(sv[PC_FAIL] > 0.0);
       double x[9];
       {
@@ -330,21 +332,24 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
 #pragma unroll
         for (int j = 0; j < 9; ++j) ok = ok && isfinite(x[j]);
       }
+      const double gmax = row16_max(gl);   // (lanes 0..15: the same in each)
+      const bool go = s_int[0] && !(gmax <= o.gradient_tolerance) && !(radius < o.min_radius);
       if (lane < 9) {
         // scaled shared step and the candidate intrinsics every worker will form from it (same expression, same bits)
         double xs = 0.0;
 #pragma unroll
         for (int j = 0; j < 9; ++j) xs = lane == j ? x[j] : xs;
         const double ds = go ? -xs : 0.0;
-        const double d = ((mask >> lane) & 1u) ? 0.0 : ds * s_ss[lane];   // the step in the intrinsics' own units
-        s_bc[2 + lane] = d;                                                 // (what the workers' unit-scaled Y and candidates take)
-        s_intr[(cur ^ 1) * 16 + lane] = s_intr[cur * 16 + lane] + d;
+        const double d = ((mask >> lane) & 1u) ? 0.0 : ds * ss_l;   // the step in the intrinsics' own units
+        s_bc[2 + lane] = d;                                          // (what the workers' unit-scaled Y and candidates take)
+        s_intr[(cur ^ 1) * 16 + lane] = k_l + d;
       }
       if (lane == 0) {
         // the flags first (they are what the broadcast waits for), the control block and the log record behind them:
         // lm_finalize below sets `done` exactly when `go` is false
         s_bc[0] = (double)((go ? 0 : 1) | (go && ok ? 2 : 0) | (hit ? 4 : 0) | (cur << 3));
         s_bc[1] = radius;
+        s_bc[12] = gmax;   // (for thread 0's bookkeeping below: not part of the broadcast)
       }
       // the broadcast leaves from THIS wave: it reads back what its own lanes have just written (a wave's LDS operations execute
       // in order), no workgroup barrier between the solve and the store the workers are waiting for
@@ -353,10 +358,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
     }
     if (tid == 0) {
       // (on the control block in LDS: only the fields lm_finalize touches move, not 144 bytes each way)
-      double gmax = sv[PC_GMAXP];
-#pragma unroll
-      for (int j = 0; j < 9; ++j)
-        if (!(mask & (1u << j))) gmax = fmax(gmax, fabs(sv[PC_GS + j]));
+      const double gmax = s_bc[12];   // (the maximum its own wave has just left there: a wave's LDS operations execute in order)
       const bool ok = ((int)s_bc[0] & 2) != 0;
       cc_iteration* e = s_int[1] ? s_log : nullptr;
       if (e && e->accepted) e->gradient_max_norm = gmax;
@@ -622,15 +624,18 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     {
       CC_FRESH_TID(tid);
       const int ncols = phase0 ? 13 : 4;
-      if (tid < 2 * ncols) {
-        const int c = tid >> 1;
+      // (from wave 2, idle here in every form -- waves 0, 5, 10, 15 are about to eliminate, the waves behind them take the pose
+      // gradients -- so that team 0's elimination does not start behind the row's LDS reads, sums and store)
+      const int stid = tid - 128;
+      if (stid >= 0 && stid < 2 * ncols) {
+        const int c = stid >> 1;
         double a = 0.0;
         if (do_sweep) {
 #pragma unroll
           for (int k = 0; k < TEAMS; ++k)
             if ((int64_t)blockIdx.x * TEAMS + k < P.F) a += s_tm[k * 192 + TM_STAT + c];
         }
-        ag_st(Q.sbox + (size_t)blockIdx.x * (2 * kPStatCols) + tid, granule(e1, a, tid & 1));
+        ag_st(Q.sbox + (size_t)blockIdx.x * (2 * kPStatCols) + stid, granule(e1, a, stid & 1));
       }
     }
     // =========================== elimination of the frame's pose block at buffer cur_e under radius_e, the workgroup's

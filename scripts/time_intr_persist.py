@@ -32,7 +32,7 @@ t = np.median(np.array(rows), axis=0)
 wn = ["round start", "pose step + Plus done", "main loop starts", "main loop done (this wave)", "all waves done", "block reduced, statistics",
       "statistics row stored", "assumed elimination + row (+ leader sum) done", "elimination done", "elimination row stored",
       "broadcast received (step if the assumption held)", "leader: sixteen rows gathered", "after a miss: step received",
-      "elimination: 6x6 factor done", "elimination: substitutions done"]
+      "elimination: 6x6 factor done", "elimination: substitutions done", "broadcast: the poll set that matched was issued"]
 cn = ["waits for statistics rows", "rows gathered", "decision taken", "decision stored / skipped", "leader rows gathered", "solve done", "step stored",
       "solve: gradient maximum", "solve: rows built", "solve: factorisation + substitutions", "solve: tests, log record, flags"]
 sk = np.median(np.array(skews), axis=0)     # [G][4]: round start, statistics stored, elimination row stored, broadcast received
