@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = [
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
     "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
+    "cc_intrinsics_set_huber", "cc_intrinsics_obs_cost", "cc_intrinsics_optimize_views_huber", "cc_intrinsics_estimate_views_huber",
+    "cc_intrinsics_batch_set_huber", "cc_intrinsics_batch_estimate_huber",
 ]
 # every symbol include/cc_harness.h declares (synthetic-input harness, host code)
 HARNESS_SYMBOLS = [
@@ -237,6 +239,18 @@ class IntrinsicsProblem:
         _check(lib().cc_intrinsics_solve(self._h, C.byref(options), C.byref(s)))
         return s.iterations
 
+    def set_huber(self, a):
+        """EXTENSION: ceres::HuberLoss(a), a in pixels, for later eval / solve / obs_cost calls (cc_intrinsics_set_huber);
+        a <= 0 switches it off. With it on the handle solves in the two-kernel form."""
+        _check(lib().cc_intrinsics_set_huber(self._h, C.c_double(a)))
+
+    def obs_cost(self):
+        """The cost of every observation at the current point, in the caller's order (cc_intrinsics_obs_cost): 1/2 rho(s) with
+        the Huber loss on, 1/2 |r|^2 with it off."""
+        out = np.zeros(self.n_obs)
+        _check(lib().cc_intrinsics_obs_cost(self._h, _p(out, C.c_double)))
+        return out
+
     def profile_sweep(self, n=50):
         ms = C.c_double()
         _check(lib().cc_intrinsics_profile_sweep(self._h, C.c_int32(n), C.byref(ms)))
@@ -298,9 +312,10 @@ def _views(off, uv, xyz):
 
 
 def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, options=None, device=0,
-                        log_capacity=1024, devices=None, views=False):
+                        log_capacity=1024, devices=None, views=False, huber_a=0.0):
     """One-shot cc_intrinsics_optimize (devices=[...]: cc_intrinsics_optimize_multi, one host thread driving several
-    devices; views=True: cc_intrinsics_optimize_views, every view handed over as its own array). Returns (intr, q, t, summary)."""
+    devices; views=True: cc_intrinsics_optimize_views, every view handed over as its own array; huber_a > 0: the extension
+    cc_intrinsics_optimize_views_huber, one device, views handed over as their own arrays). Returns (intr, q, t, summary)."""
     off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
     F = len(off) - 1
     uv, xyz = _f32(uv), _f32(xyz)
@@ -310,6 +325,14 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
     s = Summary()
     s.log = C.cast(log, C.POINTER(Iteration))
     s.log_capacity = log_capacity
+    if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
+        if devices is not None:
+            raise ValueError("huber_a is for one device only")
+        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
+        _check(lib().cc_intrinsics_optimize_views_huber(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
+                                                        _p(counts, C.c_int64), _p(intr, C.c_double), C.c_uint32(const_mask),
+                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a)))
+        return intr, q, t, _summary_dict(s, log)
     if devices is not None:
         devs = np.ascontiguousarray(devices, dtype=np.int32)
         _check(lib().cc_intrinsics_optimize_multi(C.byref(opt), C.c_int32(len(devs)), _p(devs, C.c_int32), C.c_int64(F),
@@ -331,9 +354,10 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
 
 
 def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, options=None, device=0, log_capacity=1024,
-                        views=False):
+                        views=False, huber_a=0.0):
     """cc_intrinsics_estimate (= Calibrator::Estimate: Zhang initialisation + solve, one upload; views=True:
-    cc_intrinsics_estimate_views, every view handed over as its own array and packed by the library under its upload).
+    cc_intrinsics_estimate_views, every view handed over as its own array and packed by the library under its upload;
+    huber_a > 0: the extension cc_intrinsics_estimate_views_huber, views handed over as their own arrays).
     Returns (K_init float32 3x3, intr, q, t, summary)."""
     off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
     F = len(off) - 1
@@ -346,6 +370,13 @@ def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, 
     K = np.zeros(9, dtype=np.float32)
     intr, q, t = np.zeros(9), np.zeros((F, 4)), np.zeros((F, 3))
     d5 = _f64(distortion5) if distortion5 is not None else None
+    if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
+        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
+        _check(lib().cc_intrinsics_estimate_views_huber(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
+                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
+                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
+                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a)))
+        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
     if views:
         uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
         _check(lib().cc_intrinsics_estimate_views(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
@@ -425,6 +456,16 @@ class IntrinsicsBatch:
         _check(lib().cc_intrinsics_batch_set_state(self._h, _p(intr, C.c_double), _p(mask, C.c_uint32), _p(q, C.c_double),
                                                    _p(t, C.c_double)))
 
+    def set_huber(self, a_list):
+        """EXTENSION: ceres::HuberLoss(a_list[p]), pixels, for problem p in later solves (cc_intrinsics_batch_set_huber);
+        <= 0 leaves a problem without the loss, None switches it off for all."""
+        if a_list is None:
+            _check(lib().cc_intrinsics_batch_set_huber(self._h, None))
+            return
+        a = _f64(np.asarray(a_list, dtype=np.float64).reshape(-1))
+        assert a.size == self.n_problems
+        _check(lib().cc_intrinsics_batch_set_huber(self._h, _p(a, C.c_double)))
+
     def get_state(self):
         """(intr [B][9], [q_p], [t_p]): the current point of every problem."""
         intr = np.zeros((self.n_problems, 9))
@@ -468,9 +509,10 @@ def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=Non
     return intr.reshape(B, 9), qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]
 
 
-def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024):
+def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024, huber_a=None):
     """cc_intrinsics_batch_estimate (Zhang initialisation per problem + the batched solve). distortion5: [B][5] or None;
-    const_mask: one per problem or None. Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
+    const_mask: one per problem or None; huber_a: one Huber threshold in pixels per problem (the extension
+    cc_intrinsics_batch_estimate_huber) or None. Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
     poff, foff, uv, xyz = _batch_layout(problems)
     B, F = len(poff) - 1, int(poff[-1])
     K = np.zeros((B, 9), dtype=np.float32)
@@ -479,10 +521,18 @@ def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, optio
     mask = np.zeros(B, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
     opt = options if options is not None else default_options()
     ss, logs = _batch_summaries(B, log_capacity)
-    _check(lib().cc_intrinsics_batch_estimate(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
-                                              _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                              _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                              _p(t, C.c_double), ss))
+    if huber_a is not None:
+        ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
+        assert ha.size == B
+        _check(lib().cc_intrinsics_batch_estimate_huber(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                                        _p(t, C.c_double), ss, _p(ha, C.c_double)))
+    else:
+        _check(lib().cc_intrinsics_batch_estimate(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                                  _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                                  _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                                  _p(t, C.c_double), ss))
     qs = [q[poff[p]:poff[p + 1]].copy() for p in range(B)]
     ts = [t[poff[p]:poff[p + 1]].copy() for p in range(B)]
     return K.reshape(B, 3, 3), intr, qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]

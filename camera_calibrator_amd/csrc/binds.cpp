@@ -150,6 +150,8 @@ PYBIND11_MODULE(pycalibrator, m) {
       // additions of this build
       .def("SetDevice", &Calibrator::SetDevice, py::arg("device"))
       .def("SetDevices", &Calibrator::SetDevices, py::arg("devices"))
+      .def("SetHuberLoss", &Calibrator::SetHuberLoss, py::arg("a_pixels"))   // extension: HuberLoss(a) on the reprojection residuals
+      .def("GetHuberLoss", &Calibrator::GetHuberLoss)
       .def("LastStatus", &Calibrator::LastStatus)
       .def("LastIterations", &Calibrator::LastIterations)
       .def("LastSolverReruns", &Calibrator::LastSolverReruns)

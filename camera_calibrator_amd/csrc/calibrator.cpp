@@ -102,6 +102,8 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
   const auto t_call = std::chrono::steady_clock::now();
   for (double& v : last_timing_ms_) v = 0.0;
   float K9[9];
+  if (devices_.size() > 1 && huber_a_ > 0.0)
+    throw std::invalid_argument("Calibrator::Estimate: the Huber loss (SetHuberLoss) is for one device; SetDevices selected several");
   if (devices_.size() <= 1) {
     // one device: the fused entry point (one upload of the observations for initialisation and solve together);
     // same numbers as the two calls below exchange through camera_matrix_ and the float poses. The views go over as they
@@ -123,8 +125,8 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     cc_options options;
     cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
     cc_summary summary{};
-    last_status_ = cc_intrinsics_estimate_views(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
-                                                dist5, frozen, K9, intr, qd.data(), td.data(), &summary);
+    last_status_ = cc_intrinsics_estimate_views_huber(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+                                                      dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_);   // (0: cc_intrinsics_estimate_views)
     cc_last_call_timing(&last_timing_ms_[1]);
     // Same contract as the two-step path below: environment errors (no device, HIP, exchange) and the Zhang
     // preconditions (cc_zhang_init's CC_ERR_BAD_ARGUMENT: < 3 frames, < 4 points in a frame) throw; a solver-level
@@ -208,7 +210,11 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   std::vector<double> dist5(5 * B), intr(kNumIntrinsics * B), qd(4 * F), td(3 * F);
   std::vector<uint32_t> frozen(B, 0u);
   std::vector<float> K9(9 * B);
+  std::vector<double> huber(B, 0.0);   // every calibrator's own loss (SetHuberLoss); none set: the call without one
+  bool any_huber = false;
   for (size_t p = 0; p < B; ++p) {
+    huber[p] = calibrators[p]->huber_a_;
+    any_huber = any_huber || huber[p] > 0.0;
     for (int i = 0; i < 5; ++i) dist5[5 * p + i] = calibrators[p]->distortion_(i);
     for (int idx : calibrators[p]->frozen_intrinsics_)
       if (idx >= 0 && idx < kNumIntrinsics) frozen[p] |= 1u << idx;
@@ -217,8 +223,9 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
   std::vector<cc_summary> summaries(B);
   std::memset(summaries.data(), 0, B * sizeof(cc_summary));
-  const int rc = cc_intrinsics_batch_estimate(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
-                                              dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data());
+  const int rc = cc_intrinsics_batch_estimate_huber(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                                    dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
+                                                    any_huber ? huber.data() : nullptr);
   for (size_t p = 0; p < B; ++p) calibrators[p]->last_status_ = rc;
   // the same contract as Estimate(): environment errors and the Zhang preconditions throw, a solver-level status does not
   if (rc == CC_ERR_NO_DEVICE || rc == CC_ERR_HIP || rc == CC_ERR_COMM || rc == CC_ERR_BAD_ARGUMENT)
@@ -251,6 +258,8 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
                           std::vector<Quaternion>& qs, std::vector<Point3D>& ts) {
   const size_t n_img = pixels_per_view.size();
   assert(n_img == board_points_per_view.size() && n_img == qs.size() && n_img == ts.size());
+  if (devices_.size() > 1 && huber_a_ > 0.0)
+    throw std::invalid_argument("Calibrator::Optimize: the Huber loss (SetHuberLoss) is for one device; SetDevices selected several");
   // fp64 parameter arrays; the ragged views go over as they are on one device (the library packs them under its upload),
   // as one CSR layout in cached pinned memory (one memcpy per view) for several devices
   const auto t_call = std::chrono::steady_clock::now();
@@ -287,8 +296,8 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
       xyz_views[i] = reinterpret_cast<const float*>(board_points_per_view[i].data());
       counts[i] = (int64_t)pixels_per_view[i].size();
     }
-    last_status_ = cc_intrinsics_optimize_views(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
-                                                intr, frozen, q.data(), t.data(), &summary);
+    last_status_ = cc_intrinsics_optimize_views_huber(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+                                                      intr, frozen, q.data(), t.data(), &summary, huber_a_);   // (0: cc_intrinsics_optimize_views)
     cc_last_call_timing(&last_timing_ms_[1]);
   }
   last_iterations_ = summary.iterations;
@@ -313,6 +322,11 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
   distortion_(3) = static_cast<float>(intr[P2]);
   distortion_(4) = static_cast<float>(intr[K3]);
   last_timing_ms_[6] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+}
+
+void Calibrator::SetHuberLoss(const double a_pixels) {
+  if (a_pixels != a_pixels) throw std::invalid_argument("Calibrator::SetHuberLoss: a_pixels is NaN");
+  huber_a_ = a_pixels > 0.0 ? a_pixels : 0.0;
 }
 
 void Calibrator::ForceDistortionToConstant(const int coefficient) {

@@ -60,6 +60,14 @@ class Calibrator {
   /// Several GPUs for Optimize (and the Optimize inside Estimate): the views are sharded over them and ONE host
   /// thread drives all of them (cc_intrinsics_optimize_multi). The first one also serves the point kernels.
   void SetDevices(const std::vector<int>& devices) { devices_ = devices; if (!devices.empty()) device_ = devices[0]; }
+  /// EXTENSION (the reference's Optimize sets no loss function): ceres::HuberLoss(a_pixels) with its Corrector on the reprojection
+  /// residuals of Optimize / Estimate / EstimateOpenCv / EstimateMany (there: each calibrator its own value) -- a mis-detected
+  /// corner pulls K and the distortion with a bounded force. 0 (the default) or less: off, results as without this method.
+  /// With it on the solve runs several kernels per LM iteration (LastSolverForm() == 0) on ONE device: Optimize / Estimate throw
+  /// std::invalid_argument when SetDevices selected several. NaN throws std::invalid_argument. The per-observation costs are
+  /// not exposed here (C ABI: cc_intrinsics_obs_cost).
+  void SetHuberLoss(double a_pixels);
+  double GetHuberLoss() const { return huber_a_; }
   /// Status of the last Optimize: 0 or a negative cc_status. The reference has no error channel
   /// (ceres' summary is discarded), so Optimize itself never throws on solver failure.
   int LastStatus() const { return last_status_; }
@@ -86,6 +94,7 @@ class Calibrator {
   int image_w_;
   int image_h_;
   int device_{0};
+  double huber_a_{0.0};
   std::vector<int> devices_;
   int last_status_{0};
   int last_iterations_{0};

@@ -927,6 +927,9 @@ __global__ __launch_bounds__(256) void k_intr_reset(IntrDev P, const double* ini
 
 }  // namespace cc
 
+// EXTENSION: the robust (Huber) form of the sweep and the per-observation cost kernel
+#include "cc_intrinsics_huber.hpp"
+
 // =============================================================================================
 // host side
 // =============================================================================================
@@ -960,6 +963,7 @@ struct cc_intrinsics : cc::SolveHost {   // pinned: a cached 512-byte block, hos
   cc::PersistDev pq{};
   uint32_t p_epoch = 0;         // last epoch handed to a launch (the seam words only ever see growing epochs)
   size_t p_box_bytes = 0;       // seam mailboxes (re-zeroed before the epochs wrap)
+  double huber_a = 0.0;         // EXTENSION (cc_intrinsics_set_huber): > 0 -> HuberLoss(a), pixels; the handle then solves in the two-kernel form
 };
 
 namespace cc {
@@ -977,7 +981,10 @@ static void launch_sweep(cc_intrinsics* h, bool profile, int flags = 0) {
   // the index is there when the gather is issued: A/B at 1000 x 500, sweep 17.41 vs 17.42 us, iteration 42.50 vs 42.41 us,
   // and 2 KB per frame less traffic.
   flags |= 4;
-  hipLaunchKernelGGL(k_intr_sweep, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags);
+  if (h->huber_a > 0.0)
+    hipLaunchKernelGGL(k_intr_sweep_huber, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags, h->huber_a);
+  else
+    hipLaunchKernelGGL(k_intr_sweep, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags);
 }
 
 static void launch_reset(cc_intrinsics* h) {
@@ -1082,6 +1089,7 @@ int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const fl
 
 int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]) {
   using namespace cc;
+  if (h && handle && h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_export: the handle has a Huber loss set (one device only)");
   if (int rc = exchange_export_begin(h, handle, "cc_intrinsics_exchange_export")) return rc;
   h->d.x = P2pDev{};
   return mailbox_export(&h->mailbox, kVecSolve, 16, handle);
@@ -1091,6 +1099,7 @@ int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks
   using namespace cc;
   if (!h || !handles || rank < 0 || nranks < 1 || rank >= nranks || nranks > kP2pMaxRanks)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_exchange_attach: bad arguments (nranks must be 1..%d)", kP2pMaxRanks);
+  if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: the handle has a Huber loss set (one device only)");
   if (!h->mailbox.local) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: call cc_intrinsics_exchange_export first");
   if (h->comm) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: an RCCL communicator is already attached");
   CC_HIP(hipSetDevice(h->device));
@@ -1278,6 +1287,8 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   h->elim_blocks = (int)std::min<int64_t>(kElimMaxBlocks, (F + 15) / 16);
   CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intr_sweep),
                              hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
+  CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intr_sweep_huber),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
   return CC_OK;
 }
 }  // namespace cc
@@ -1397,6 +1408,41 @@ int cc_intrinsics_eval(cc_intrinsics* h, double* blocks, double* cost) {
   return CC_OK;
 }
 
+// EXTENSION: ceres::HuberLoss(a_pixels) for later eval / solve / obs_cost calls (cc_intrinsics_huber.hpp). a <= 0: off.
+int cc_intrinsics_set_huber(cc_intrinsics* h, double a_pixels) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_huber: NULL handle");
+  if (a_pixels != a_pixels) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_huber: a_pixels is NaN");
+  if (h->exchange || h->comm || h->mailbox.local)
+    return fail(CC_ERR_STATE, "cc_intrinsics_set_huber: the handle has an exchange or a communicator attached (the loss is for one device only)");
+  const double a = a_pixels > 0.0 ? a_pixels : 0.0;
+  if (a != h->huber_a) drop_graphs(h);   // kernel and arguments are baked into the graphs
+  h->huber_a = a;
+  return CC_OK;
+}
+
+// EXTENSION: the cost of every observation at the current point, in the caller's order: 1/2 rho(s) with the loss on, 1/2 s without.
+int cc_intrinsics_obs_cost(cc_intrinsics* h, double* obs_cost) {
+  using namespace cc;
+  if (!h || !obs_cost) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_obs_cost: NULL argument");
+  if (!h->have_state) return fail(CC_ERR_STATE, "cc_intrinsics_obs_cost: no state set");
+  if (h->N == 0) return CC_OK;
+  CC_HIP(hipSetDevice(h->device));
+  LmCtl st;
+  if (int rc = read_ctl(h, &st)) return rc;
+  const int64_t cost_blocks = (h->N + 255) / 256;
+  if (cost_blocks > (int64_t)INT32_MAX) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_obs_cost: %lld observations exceed the launch grid", (long long)h->N);
+  double* d_out = nullptr;
+  CC_HIP(hipMalloc(&d_out, (size_t)h->N * sizeof(double)));
+  hipLaunchKernelGGL(k_intr_obs_cost, dim3((unsigned)cost_blocks), dim3(256), 0, h->stream, h->d, st.cur & 1, h->huber_a, d_out);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(obs_cost, d_out, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  hipFree(d_out);
+  CC_HIP(e);
+  return CC_OK;
+}
+
 }  // extern "C"
 
 namespace cc {
@@ -1485,7 +1531,7 @@ static int solve_wait(cc_intrinsics* h, SolveRun* r) {
 // The whole solve as one launch of the persistent kernel. Starts from buffer 0 (solve_begin moved a continued solve's
 // accepted point there) or, after set_state / reset, from the initial-state arrays.
 static bool use_persistent(const cc_intrinsics* h, const SolveRun* r) {
-  return !h->comm && !r->profile && (h->exchange ? h->persist_x_ok : h->persist_ok);
+  return !h->comm && !r->profile && !(h->huber_a > 0.0) && (h->exchange ? h->persist_x_ok : h->persist_ok);
 }
 
 static int persistent_launch(cc_intrinsics* h, SolveRun* r) {
@@ -1693,7 +1739,7 @@ int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, i
 }
 
 int cc_intrinsics_solver_form(cc_intrinsics* h) {
-  if (!h || h->comm) return 0;
+  if (!h || h->comm || h->huber_a > 0.0) return 0;   // (the robust sweep exists in the two-kernel form only)
   return (h->exchange ? h->persist_x_ok : h->persist_ok) ? h->pq.teams : 0;
 }
 
@@ -1707,6 +1753,7 @@ int cc_intrinsics_profile_solve(cc_intrinsics* h, const cc_options* opt, int32_t
   using namespace cc;
   if (!h || n < 1 || !avg_launch_ms) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_profile_solve: bad arguments");
   if (!h->have_state) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: no state set");
+  if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: the handle has a Huber loss set and solves in the two-kernel form");
   if (!h->persist_ok || h->comm || h->exchange) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: the handle does not use the persistent form on a device of its own");
   CC_HIP(hipSetDevice(h->device));
   hipEvent_t e0, e1;
@@ -1984,36 +2031,48 @@ struct ViewsUpload {
 };
 }  // namespace cc
 
-int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                 const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                 float* K_init9, double* intr9, double* q, double* t, cc_summary* summary) {
+// (cc_intrinsics_estimate_views is this with huber_a = 0: the same path, bit for bit)
+int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a) {
   cc::last_call_status_reset();
   using namespace cc;
   if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views: needs >= 3 views and non-NULL arrays");
+  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_huber: huber_a is NaN");
   const ZhangScratch zs(F);
   double* tm = last_timing();
   for (int i = 0; i < 5; ++i) tm[i] = 0.0;
   ViewsUpload up;
   if (int rc = up.open("cc_intrinsics_estimate_views", device, F, uv_views, xyz_views, counts, 4, zs.bytes)) return rc;
+  if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = estimate_on_handle(up.h, zs, opt, F, distortion5, mask, K_init9, intr9, q, t, summary, t0);
   if (rc) (void)hipStreamSynchronize(up.h->stream);   // (an early return may have left copies from the staging block in flight)
   return rc;
 }
 
+int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                 const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                 float* K_init9, double* intr9, double* q, double* t, cc_summary* summary) {
+  return cc_intrinsics_estimate_views_huber(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, 0.0);
+}
+
 // cc_intrinsics_optimize for views given as separate arrays (Calibrator::Optimize's arguments, calibrator.cpp:70-74).
-int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                 const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
-                                 double* q, double* t, cc_summary* summary) {
+// (cc_intrinsics_optimize_views is this with huber_a = 0: the same path, bit for bit)
+int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                       double* q, double* t, cc_summary* summary, double huber_a) {
   cc::last_call_status_reset();
   using namespace cc;
   if (F < 1 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views: needs >= 1 view and non-NULL arrays");
+  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_huber: huber_a is NaN");
   double* tm = last_timing();
   for (int i = 0; i < 5; ++i) tm[i] = 0.0;
   ViewsUpload up;
   if (int rc = up.open("cc_intrinsics_optimize_views", device, F, uv_views, xyz_views, counts, 0, 0)) return rc;
+  if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
   auto t0 = std::chrono::steady_clock::now();
   int rc = CC_OK;
   if (hipStreamSynchronize(up.h->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(CC_ERR_HIP, "upload failed"); }
@@ -2029,10 +2088,17 @@ int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t 
   return rc;
 }
 
+int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                 const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                 double* q, double* t, cc_summary* summary) {
+  return cc_intrinsics_optimize_views_huber(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, 0.0);
+}
+
 int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t rank, int32_t nranks) {
   using namespace cc;
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_comm_init: bad arguments (nranks must be 1..32)");
+  if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_comm_init: the handle has a Huber loss set (one device only)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
   drop_graphs(h);

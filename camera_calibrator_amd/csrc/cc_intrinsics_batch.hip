@@ -19,6 +19,7 @@
 #include "cc_common.hpp"
 #include "cc_device.hpp"
 #include "cc_intrinsics_dev.hpp"
+#include "cc_intrinsics_batch_dev.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -28,30 +29,7 @@
 namespace cc {
 
 constexpr int kBatchLogCap = 1024;   // log records per problem on the device (max_iterations is clamped to this - 1)
-
-struct IntrBatchDev {
-  int64_t N;               // observations of all problems
-  int32_t B, Ftot;         // problems, frames of all problems
-  const float* uv;
-  const float* xyz;
-  const int64_t* off;      // [Ftot + 1] frame -> observations
-  const int2* where;       // [Ftot] sweep workgroup -> {problem, local frame}
-  const int32_t* first;    // [B + 1] problem -> frames
-  const uint32_t* mask;    // [B]
-  double* intr;            // [B][2][16]
-  double* pose;            // [2][Ftot][8]
-  double* blocks;          // [2][Ftot][256]
-  double* stats;           // [Ftot][4]
-  double* hd0;             // [Ftot][16] diag of H_ss at the initial point (Jacobi scaling)
-  double* sp;              // [Ftot][8]  Jacobi scale of the pose block
-  double* Y;               // [Ftot][64]
-  double* ds;              // [B][16] scaled shared step
-  double* ss;              // [B][16] Jacobi scale of the shared block
-  LmCtl* ctl;              // [B]
-  const LmOpts* opts;      // one set of options for the whole batch
-  cc_iteration* log;       // [log_cap][B]: record r of problem p at r * B + p (one transfer reads the used rows of all)
-  int32_t log_cap, pad_;
-};
+// (IntrBatchDev, the device view of a batch: cc_intrinsics_batch_dev.hpp)
 
 // ---------------------------------------------------------------------------------------------
 // batch sweep: k_intr_sweep for the frame of one problem of the batch (one tile per frame, current Gram buffer only)
@@ -618,6 +596,9 @@ struct cc_intrinsics_batch {
   uint32_t* d_mask = nullptr;
   cc::LmOpts h_opts{};             // source of the options' upload (alive until the solve's first wait)
   bool have_state = false;
+  double* d_huber = nullptr;       // EXTENSION (cc_intrinsics_batch_set_huber): [B] HuberLoss(a) per problem, pixels; <= 0: off
+  bool huber_on = false;           // ... on for at least one problem: the solve launches k_intrb_sweep_huber behind k_intrb_sweep
+  bool huber_all = false;          // ... on for every problem: k_intrb_sweep has nothing to sweep and is left out
 };
 
 namespace cc {
@@ -651,6 +632,7 @@ static int batch_create_impl(cc_intrinsics_batch* h, const int64_t* frame_offset
   const size_t o_ctl = take(B * sizeof(LmCtl));
   const size_t o_opts = take(sizeof(LmOpts));
   const size_t o_mask = take(B * sizeof(uint32_t));
+  const size_t o_huber = take(B * sizeof(double));
   const size_t zeroed = cursor;   // everything above starts as zeros
   const size_t o_blocks = take(2 * F * 256 * sizeof(double));
   const size_t o_log = take((size_t)kBatchLogCap * B * sizeof(cc_iteration));
@@ -682,6 +664,7 @@ static int batch_create_impl(cc_intrinsics_batch* h, const int64_t* frame_offset
   d.first = reinterpret_cast<const int32_t*>(base + o_first);
   h->d_mask = reinterpret_cast<uint32_t*>(base + o_mask);
   d.mask = h->d_mask;
+  h->d_huber = reinterpret_cast<double*>(base + o_huber);
   d.intr = reinterpret_cast<double*>(base + o_intr);
   d.pose = reinterpret_cast<double*>(base + o_pose);
   d.blocks = reinterpret_cast<double*>(base + o_blocks);
@@ -697,6 +680,7 @@ static int batch_create_impl(cc_intrinsics_batch* h, const int64_t* frame_offset
   d.log_cap = kBatchLogCap;
   d.pad_ = 0;
   CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intrb_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
+  if (int rc = batch_sweep_huber_prepare()) return rc;
   return CC_OK;
 }
 
@@ -754,6 +738,27 @@ int cc_intrinsics_batch_set_state(cc_intrinsics_batch* h, const double* intr9, c
   return CC_OK;
 }
 
+// EXTENSION: ceres::HuberLoss(a_pixels[p]) for problem p in later solves (cc_intrinsics_huber.hpp); <= 0: off, NULL: all off.
+int cc_intrinsics_batch_set_huber(cc_intrinsics_batch* h, const double* a_pixels) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_set_huber: NULL handle");
+  std::vector<double> a((size_t)h->B, 0.0);
+  bool on = false, all = a_pixels != nullptr;
+  if (a_pixels)
+    for (int64_t p = 0; p < h->B; ++p) {
+      if (a_pixels[p] != a_pixels[p]) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_set_huber: a_pixels[%lld] is NaN", (long long)p);
+      a[(size_t)p] = a_pixels[p] > 0.0 ? a_pixels[p] : 0.0;
+      on = on || a_pixels[p] > 0.0;
+      all = all && a_pixels[p] > 0.0;
+    }
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  CC_HIP(hipMemcpy(h->d_huber, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->huber_on = on;
+  h->huber_all = all;
+  return CC_OK;
+}
+
 int cc_intrinsics_batch_get_state(cc_intrinsics_batch* h, double* intr9, double* q, double* t) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_get_state: NULL handle");
@@ -802,7 +807,10 @@ int cc_intrinsics_batch_solve(cc_intrinsics_batch* h, const cc_options* opt, cc_
     // plain launches, stream order only; the first chunk holds the initial evaluation plus check_interval iterations
     const int n = o.check_interval + (chunk == 0 ? 1 : 0);
     for (int i = 0; i < n; ++i) {
-      hipLaunchKernelGGL(k_intrb_sweep, dim3((unsigned)h->Ftot), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d);
+      // (EXTENSION, cc_intrinsics_batch_huber.hip: the problems with a Huber loss are swept again by the robust kernel, which
+      // overwrites their blocks and statistics; the plain ones keep k_intrb_sweep's bits)
+      if (!h->huber_all) hipLaunchKernelGGL(k_intrb_sweep, dim3((unsigned)h->Ftot), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d);
+      if (h->huber_on) batch_sweep_huber_launch(h->d, h->d_huber, h->stream);
       hipLaunchKernelGGL(k_intrb_step, dim3((unsigned)B), dim3(256), 0, h->stream, h->d);
     }
     CC_HIP(hipGetLastError());
@@ -858,12 +866,17 @@ int cc_intrinsics_batch_optimize(const cc_options* opt, int32_t device, int64_t 
 // Calibrator::Estimate for every problem of the batch: Zhang's closed-form initialisation per problem on the handle's
 // device arrays (zhang_on_device, same stream), its K and poses rounded to float as cc_intrinsics_estimate hands them
 // over, then the batched solve. distortion5 [B][5] (may be NULL: zeros), const_mask [B] (may be NULL), K_init9 [B][9] (may be NULL).
-int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
-                                 const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
-                                 const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries) {
+// (huber_a [B] or NULL: EXTENSION, a Huber loss per problem; cc_intrinsics_batch_estimate is this with NULL -- the same path, bit for bit)
+int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
+                                       const double* huber_a) {
   using namespace cc;
   const char* who = "cc_intrinsics_batch_estimate";
   if (!intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: intr9 / q / t are NULL", who);
+  if (huber_a)
+    for (int64_t p = 0; p < n_problems; ++p)
+      if (huber_a[p] != huber_a[p]) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a[%lld] is NaN", who, (long long)p);
   {   // the Zhang preconditions, before any device call
     std::vector<int32_t> first, where;
     if (int rc = batch_build_tables(who, n_problems, problem_offsets, frame_offsets, &first, &where)) return rc;
@@ -904,9 +917,17 @@ int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t 
   for (size_t i = 0; i < qf.size(); ++i) q[i] = qf[i];
   for (size_t i = 0; i < tf.size(); ++i) t[i] = tf[i];
   int rc = cc_intrinsics_batch_set_state(h, intr9, const_mask, q, t);
+  if (!rc && huber_a) rc = cc_intrinsics_batch_set_huber(h, huber_a);
   if (!rc) rc = cc_intrinsics_batch_solve(h, opt, summaries);
   if (!rc) rc = cc_intrinsics_batch_get_state(h, intr9, q, t);
   return rc;
+}
+
+int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                 const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                 const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries) {
+  return cc_intrinsics_batch_estimate_huber(opt, device, n_problems, problem_offsets, frame_offsets, uv, xyz, distortion5, const_mask,
+                                            K_init9, intr9, q, t, summaries, nullptr);
 }
 
 }  // extern "C"

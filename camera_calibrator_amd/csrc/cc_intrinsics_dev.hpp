@@ -119,6 +119,23 @@ __device__ __forceinline__ void row_v(const double* k, const ObsCommon& c, doubl
 // entry e = 16 row + col of a frame's 16 x 16 Gram block: does it belong to a coordinate held constant (mask bit j = intrinsic j)?
 __device__ __forceinline__ bool gram_entry_held(uint32_t mask, int e) { return (((mask >> (e >> 4)) | (mask >> (e & 15))) & 1u) != 0; }
 
+// EXTENSION (cc_intrinsics_huber.hpp): ceres::HuberLoss(a) at s = |r|^2 -- rho and the row weight sqrt(rho') of the robust
+// sweeps. The tail in the form of the rig path's huber() (cc_rig.hip; a local copy, as rig_inner_huber is): |r| = s y and
+// sqrt(a / |r|) = q rsqrt(q), q = a y, from two refined reciprocal square roots. Both branches are computed and two values
+// selected -- most waves of a dirty frame hold an outlier anyway. A non-finite s gives a non-finite rho (NaN stays NaN,
+// +inf: inf * 0); a = +inf never reaches the tail.
+__device__ __forceinline__ void intr_huber(double a, double s, double& rho, double& sr) {
+  const double b = a * a;
+  const double y = rsqrt_pos(s);
+  const double r = s * y;
+  const double q = fmax(2.2250738585072014e-308, a * y);
+  const double tail_sr = q * rsqrt_pos(q);
+  const double tail_rho = 2.0 * a * r - b;
+  const bool tail = s > b;
+  rho = tail ? tail_rho : s;
+  sr = tail ? tail_sr : 1.0;
+}
+
 // Hands the control block to the host without a copy engine in the way: payload words first, then the
 // sequence word the host spins on (system-scope stores into pinned host memory; one thread).
 __device__ __forceinline__ void publish_to_host(const IntrDev& P, const LmCtl& c) {

@@ -257,6 +257,35 @@ int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]);
 int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks, const uint8_t* handles);
 
 /* ---------------------------------------------------------------------------------------------
+ * EXTENSION (the reference's Calibrator::Optimize sets no loss function, calibrator.cpp:236-324; the rig path has carried
+ * Ceres' HuberLoss from the start): ceres::HuberLoss(a) with its Corrector for the single-camera solve, a in PIXELS, off by
+ * default. Per observation s = ru^2 + rv^2; rho(s) = s for s <= a^2, else 2 a sqrt(s) - a^2; cost = 1/2 sum rho(s); the
+ * observation's two Jacobian rows and its residual are multiplied by sqrt(rho'(s)) (1 up to a^2, sqrt(a / sqrt(s)) beyond;
+ * rho'' <= 0, so the Corrector has no second-order term). One mis-detected corner then pulls K and the distortion with a
+ * bounded force. a <= 0: off (every entry point returns the bits it returned before the loss existed); NaN:
+ * CC_ERR_BAD_ARGUMENT; +inf: allowed, no observation is ever in the tail. A non-finite residual still makes the cost
+ * non-finite and ends the solve as it does with the loss off.
+ * Out of scope: the persistent per-solve kernel, every multi-GPU form, losses other than Huber.
+ * ------------------------------------------------------------------------------------------- */
+/* Applies to later cc_intrinsics_eval / _solve / _obs_cost calls. With a > 0 the handle solves in the two-kernel form by choice
+ * (cc_intrinsics_solver_form reports 0; no give-up, no device back-off entry, reruns stays 0) and a captured graph is dropped;
+ * a <= 0 gives the handle back the form it had. CC_ERR_STATE on a handle with an exchange or communicator attached;
+ * cc_intrinsics_exchange_export / _attach, cc_intrinsics_comm_init and cc_intrinsics_profile_solve return CC_ERR_STATE on a
+ * handle with the loss on. */
+int cc_intrinsics_set_huber(cc_intrinsics* h, double a_pixels);
+/* obs_cost [N]: the cost of every observation at the current point, in the caller's order -- 1/2 rho(s) with the loss on,
+ * 1/2 s with it off. */
+int cc_intrinsics_obs_cost(cc_intrinsics* h, double* obs_cost);
+/* cc_intrinsics_optimize_views / cc_intrinsics_estimate_views with a trailing huber_a (those two ARE these with 0). */
+int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t n_frames, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t const_mask,
+                                       double* q_wxyz, double* t_xyz, cc_summary* summary, double huber_a);
+int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t n_frames, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5,
+                                       uint32_t const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summary, double huber_a);
+
+/* ---------------------------------------------------------------------------------------------
  * EXTENSION (nothing in the reference does it): a BATCH of independent single-camera problems solved together on one
  * device -- a rig's cameras before the rig solve (system_calibration.py runs optimize_intrinsics camera by camera,
  * cam_calibration.py:290-314), leave-one-view-out and bootstrap runs, subset fits. Problem p owns frames
@@ -296,6 +325,15 @@ int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t 
                                  const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
                                  const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
                                  cc_summary* summaries);
+/* EXTENSION: the Huber loss of cc_intrinsics_set_huber per problem, a_pixels [B] (NULL: all off), for later solves. A problem
+ * with a <= 0 keeps, bit for bit, what a batch without any loss returns for it; bad arguments (NULL handle, a NaN) are
+ * refused before any device call. cc_intrinsics_batch_estimate_huber: cc_intrinsics_batch_estimate with huber_a [B] or NULL
+ * (cc_intrinsics_batch_estimate IS it with NULL). */
+int cc_intrinsics_batch_set_huber(cc_intrinsics_batch* h, const double* a_pixels);
+int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summaries, const double* huber_a);
 
 /* Contiguous frame partition balanced by observation count (host logic, no GPU needed).
  * first_frame has nranks+1 entries; rank r owns frames [first_frame[r], first_frame[r+1]). */

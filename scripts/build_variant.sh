@@ -25,7 +25,7 @@ cp $root/include/*.h $work/include/
 for p in "${patches[@]}"; do (cd $work/camera_calibrator_amd && patch -s -p0 < $root/scripts/variants/$p.patch); done
 (cd $work/camera_calibrator_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-result -Wno-unused-value "${flags[@]}" -c $file -o /tmp/cc_variant_$name.o)
 objs=""
-for o in cc_intrinsics.o cc_intrinsics_batch.o cc_intrinsics_persist.o cc_rig.o cc_rig_inner.o cc_zhang.o cc_points.o cc_common.o cc_comm.o data_generator.o rig_scenario.o geometry.o; do
+for o in $(sed -n 's/^OBJS *= *//p' $src/Makefile); do   # (the Makefile's list: a new translation unit is linked here too)
   if [ "$o" = "${file%.hip}.o" ]; then objs="$objs /tmp/cc_variant_$name.o"; else objs="$objs $src/$o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libcc_$name.so $objs -ldl -pthread -Wl,-rpath,/opt/rocm/lib
