@@ -91,7 +91,11 @@ EXPORTED_SYMBOLS = [
     "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
     "cc_intrinsics_set_huber", "cc_intrinsics_obs_cost", "cc_intrinsics_optimize_views_huber", "cc_intrinsics_estimate_views_huber",
     "cc_intrinsics_batch_set_huber", "cc_intrinsics_batch_estimate_huber",
+    "cc_intrinsics_set_model", "cc_intrinsics_get_model", "cc_intrinsics_optimize_views_model", "cc_intrinsics_estimate_views_model",
+    "cc_distort_fisheye", "cc_undistort_fisheye",
 ]
+# EXTENSION: camera models of the single-camera solve (cc_solver.h)
+MODEL_RADTAN, MODEL_FISHEYE = 0, 1
 # every symbol include/cc_harness.h declares (synthetic-input harness, host code)
 HARNESS_SYMBOLS = [
     "cc_generator_create", "cc_generator_destroy", "cc_generator_set_k", "cc_generator_set_distortion",
@@ -244,6 +248,15 @@ class IntrinsicsProblem:
         a <= 0 switches it off. With it on the handle solves in the two-kernel form."""
         _check(lib().cc_intrinsics_set_huber(self._h, C.c_double(a)))
 
+    def set_model(self, model):
+        """EXTENSION: the camera model of later set_state / eval / solve / obs_cost calls (cc_intrinsics_set_model):
+        MODEL_RADTAN (the default) or MODEL_FISHEYE (slots fx fy px py k1 k2 k3 k4 -, slot 8 held at 0; two-kernel form).
+        A change drops the state: call set_state next."""
+        _check(lib().cc_intrinsics_set_model(self._h, C.c_int32(model)))
+
+    def get_model(self):
+        return int(lib().cc_intrinsics_get_model(self._h))
+
     def obs_cost(self):
         """The cost of every observation at the current point, in the caller's order (cc_intrinsics_obs_cost): 1/2 rho(s) with
         the Huber loss on, 1/2 |r|^2 with it off."""
@@ -312,10 +325,11 @@ def _views(off, uv, xyz):
 
 
 def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, options=None, device=0,
-                        log_capacity=1024, devices=None, views=False, huber_a=0.0):
+                        log_capacity=1024, devices=None, views=False, huber_a=0.0, model=0):
     """One-shot cc_intrinsics_optimize (devices=[...]: cc_intrinsics_optimize_multi, one host thread driving several
     devices; views=True: cc_intrinsics_optimize_views, every view handed over as its own array; huber_a > 0: the extension
-    cc_intrinsics_optimize_views_huber, one device, views handed over as their own arrays). Returns (intr, q, t, summary)."""
+    cc_intrinsics_optimize_views_huber, one device, views handed over as their own arrays; model != 0: the extension
+    cc_intrinsics_optimize_views_model, likewise, with huber_a passed on). Returns (intr, q, t, summary)."""
     off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
     F = len(off) - 1
     uv, xyz = _f32(uv), _f32(xyz)
@@ -325,6 +339,15 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
     s = Summary()
     s.log = C.cast(log, C.POINTER(Iteration))
     s.log_capacity = log_capacity
+    if model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
+        if devices is not None:
+            raise ValueError("model is for one device only")
+        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
+        _check(lib().cc_intrinsics_optimize_views_model(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
+                                                        _p(counts, C.c_int64), _p(intr, C.c_double), C.c_uint32(const_mask),
+                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
+                                                        C.c_int32(model)))
+        return intr, q, t, _summary_dict(s, log)
     if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
         if devices is not None:
             raise ValueError("huber_a is for one device only")
@@ -354,10 +377,11 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
 
 
 def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, options=None, device=0, log_capacity=1024,
-                        views=False, huber_a=0.0):
+                        views=False, huber_a=0.0, model=0):
     """cc_intrinsics_estimate (= Calibrator::Estimate: Zhang initialisation + solve, one upload; views=True:
     cc_intrinsics_estimate_views, every view handed over as its own array and packed by the library under its upload;
-    huber_a > 0: the extension cc_intrinsics_estimate_views_huber, views handed over as their own arrays).
+    huber_a > 0: the extension cc_intrinsics_estimate_views_huber, views handed over as their own arrays; model != 0: the
+    extension cc_intrinsics_estimate_views_model, likewise, `distortion5` then holding the model's coefficients).
     Returns (K_init float32 3x3, intr, q, t, summary)."""
     off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
     F = len(off) - 1
@@ -370,6 +394,14 @@ def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, 
     K = np.zeros(9, dtype=np.float32)
     intr, q, t = np.zeros(9), np.zeros((F, 4)), np.zeros((F, 3))
     d5 = _f64(distortion5) if distortion5 is not None else None
+    if model != 0:   # (0 is off: the symbols without a model argument, below)
+        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
+        _check(lib().cc_intrinsics_estimate_views_model(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
+                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
+                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
+                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
+                                                        C.c_int32(model)))
+        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
     if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
         uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
         _check(lib().cc_intrinsics_estimate_views_huber(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
@@ -825,17 +857,31 @@ def zhang_init(frame_offsets, uv, xyz, device=0, want_homographies=False):
     return (K.reshape(3, 3), q, t, H) if want_homographies else (K.reshape(3, 3), q, t)
 
 
-def distort(K, dist, xy, device=0):
+def distort(K, dist, xy, device=0, model=0):
+    """cc_distort; model=MODEL_FISHEYE: the extension cc_distort_fisheye, dist = k1 k2 k3 k4."""
     xy = _f32(xy)
     out = np.zeros_like(xy)
+    if model != 0:
+        if model != MODEL_FISHEYE:
+            raise ValueError(f"unknown model {model}")
+        _check(lib().cc_distort_fisheye(C.c_int32(device), _p(_f32(K), C.c_float), _p(_f32(np.asarray(dist).reshape(-1)[:4]), C.c_float),
+                                        C.c_int64(xy.size // 2), _p(xy, C.c_float), _p(out, C.c_float)))
+        return out
     _check(lib().cc_distort(C.c_int32(device), _p(_f32(K), C.c_float), _p(_f32(dist), C.c_float),
                             C.c_int64(xy.size // 2), _p(xy, C.c_float), _p(out, C.c_float)))
     return out
 
 
-def undistort(K, dist, uv, device=0):
+def undistort(K, dist, uv, device=0, model=0):
+    """cc_undistort; model=MODEL_FISHEYE: the extension cc_undistort_fisheye, dist = k1 k2 k3 k4."""
     uv = _f32(uv)
     out = np.zeros_like(uv)
+    if model != 0:
+        if model != MODEL_FISHEYE:
+            raise ValueError(f"unknown model {model}")
+        _check(lib().cc_undistort_fisheye(C.c_int32(device), _p(_f32(K), C.c_float), _p(_f32(np.asarray(dist).reshape(-1)[:4]), C.c_float),
+                                          C.c_int64(uv.size // 2), _p(uv, C.c_float), _p(out, C.c_float)))
+        return out
     _check(lib().cc_undistort(C.c_int32(device), _p(_f32(K), C.c_float), _p(_f32(dist), C.c_float),
                               C.c_int64(uv.size // 2), _p(uv, C.c_float), _p(out, C.c_float)))
     return out

@@ -135,6 +135,9 @@ PYBIND11_MODULE(pycalibrator, m) {
   using calibrator::Calibrator;
   using calibrator::ExtrinsicsCalibrator;
 
+  py::enum_<calibrator::CameraModel>(m, "CameraModel")   // extension: lens models of Calibrator::SetCameraModel
+      .value("RadTan", calibrator::CameraModel::RadTan)
+      .value("Fisheye", calibrator::CameraModel::Fisheye);
   py::class_<Calibrator>(m, "Calibrator")
       .def(py::init<int, int>())
       .def("EstimateOpenCv", &Calibrator::EstimateOpenCv, py::arg("img_points"), py::arg("world_points"))
@@ -152,6 +155,8 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("SetDevices", &Calibrator::SetDevices, py::arg("devices"))
       .def("SetHuberLoss", &Calibrator::SetHuberLoss, py::arg("a_pixels"))   // extension: HuberLoss(a) on the reprojection residuals
       .def("GetHuberLoss", &Calibrator::GetHuberLoss)
+      .def("SetCameraModel", &Calibrator::SetCameraModel, py::arg("model"))   // extension: CameraModel.Fisheye = Kannala-Brandt
+      .def("GetCameraModel", &Calibrator::GetCameraModel)
       .def("LastStatus", &Calibrator::LastStatus)
       .def("LastIterations", &Calibrator::LastIterations)
       .def("LastSolverReruns", &Calibrator::LastSolverReruns)

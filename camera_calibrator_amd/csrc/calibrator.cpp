@@ -85,7 +85,7 @@ void Calibrator::EstimateOpenCv(const std::vector<Points2D>& pixels_per_view, co
   (void)image_h_;
   const std::set<int> held = frozen_intrinsics_;
   frozen_intrinsics_.clear();
-  distortion_ = DynamicVector::Zero(5);
+  distortion_ = DynamicVector::Zero(model_ == CameraModel::Fisheye ? 4 : 5);
   try {
     Estimate(pixels_per_view, board_points_per_view);
   } catch (...) {
@@ -104,12 +104,14 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
   float K9[9];
   if (devices_.size() > 1 && huber_a_ > 0.0)
     throw std::invalid_argument("Calibrator::Estimate: the Huber loss (SetHuberLoss) is for one device; SetDevices selected several");
+  if (devices_.size() > 1 && model_ != CameraModel::RadTan)
+    throw std::invalid_argument("Calibrator::Estimate: the fisheye model (SetCameraModel) is for one device; SetDevices selected several");
   if (devices_.size() <= 1) {
     // one device: the fused entry point (one upload of the observations for initialisation and solve together);
     // same numbers as the two calls below exchange through camera_matrix_ and the float poses. The views go over as they
     // are (one pointer per view): the library packs them into pinned memory piece by piece under the upload.
     double intr[kNumIntrinsics], dist5[5];
-    for (int i = 0; i < 5; ++i) dist5[i] = distortion_(i);
+    for (int i = 0; i < 5; ++i) dist5[i] = i < distortion_.size() ? distortion_(i) : 0.0f;   // (fisheye: four coefficients)
     uint32_t frozen = 0;
     for (int idx : frozen_intrinsics_)
       if (idx >= 0 && idx < kNumIntrinsics) frozen |= 1u << idx;
@@ -125,8 +127,9 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     cc_options options;
     cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
     cc_summary summary{};
-    last_status_ = cc_intrinsics_estimate_views_huber(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
-                                                      dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_);   // (0: cc_intrinsics_estimate_views)
+    last_status_ = cc_intrinsics_estimate_views_model(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+                                                      dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_,
+                                                      static_cast<int32_t>(model_));   // (0, RadTan: cc_intrinsics_estimate_views)
     cc_last_call_timing(&last_timing_ms_[1]);
     // Same contract as the two-step path below: environment errors (no device, HIP, exchange) and the Zhang
     // preconditions (cc_zhang_init's CC_ERR_BAD_ARGUMENT: < 3 frames, < 4 points in a frame) throw; a solver-level
@@ -143,11 +146,7 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     camera_matrix_(1, 1) = static_cast<float>(intr[FY]);
     camera_matrix_(0, 2) = static_cast<float>(intr[PX]);
     camera_matrix_(1, 2) = static_cast<float>(intr[PY]);
-    distortion_(0) = static_cast<float>(intr[K1]);
-    distortion_(1) = static_cast<float>(intr[K2]);
-    distortion_(2) = static_cast<float>(intr[P1]);
-    distortion_(3) = static_cast<float>(intr[P2]);
-    distortion_(4) = static_cast<float>(intr[K3]);
+    WriteBackDistortion(intr);
     last_timing_ms_[6] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return;
   }
@@ -212,6 +211,9 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   std::vector<float> K9(9 * B);
   std::vector<double> huber(B, 0.0);   // every calibrator's own loss (SetHuberLoss); none set: the call without one
   bool any_huber = false;
+  for (size_t p = 0; p < B; ++p)   // (the batch carries the radial-tangential model only: refused before anything is packed for the device)
+    if (calibrators[p] && calibrators[p]->model_ != CameraModel::RadTan)
+      throw std::invalid_argument("Calibrator::EstimateMany: a calibrator has the fisheye model set (SetCameraModel); the batch is radial-tangential only");
   for (size_t p = 0; p < B; ++p) {
     huber[p] = calibrators[p]->huber_a_;
     any_huber = any_huber || huber[p] > 0.0;
@@ -260,6 +262,8 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
   assert(n_img == board_points_per_view.size() && n_img == qs.size() && n_img == ts.size());
   if (devices_.size() > 1 && huber_a_ > 0.0)
     throw std::invalid_argument("Calibrator::Optimize: the Huber loss (SetHuberLoss) is for one device; SetDevices selected several");
+  if (devices_.size() > 1 && model_ != CameraModel::RadTan)
+    throw std::invalid_argument("Calibrator::Optimize: the fisheye model (SetCameraModel) is for one device; SetDevices selected several");
   // fp64 parameter arrays; the ragged views go over as they are on one device (the library packs them under its upload),
   // as one CSR layout in cached pinned memory (one memcpy per view) for several devices
   const auto t_call = std::chrono::steady_clock::now();
@@ -271,7 +275,7 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
   }
   double intr[kNumIntrinsics];
   intr[FX] = camera_matrix_(0, 0); intr[FY] = camera_matrix_(1, 1); intr[PX] = camera_matrix_(0, 2); intr[PY] = camera_matrix_(1, 2);
-  intr[K1] = distortion_(0); intr[K2] = distortion_(1); intr[P1] = distortion_(2); intr[P2] = distortion_(3); intr[K3] = distortion_(4);
+  for (int i = 0; i < 5; ++i) intr[K1 + i] = i < distortion_.size() ? distortion_(i) : 0.0f;   // (k1 k2 p1 p2 k3, or the fisheye model's k1..k4 and 0)
   uint32_t frozen = 0;
   for (int idx : frozen_intrinsics_)
     if (idx >= 0 && idx < kNumIntrinsics) frozen |= 1u << idx;
@@ -296,8 +300,9 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
       xyz_views[i] = reinterpret_cast<const float*>(board_points_per_view[i].data());
       counts[i] = (int64_t)pixels_per_view[i].size();
     }
-    last_status_ = cc_intrinsics_optimize_views_huber(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
-                                                      intr, frozen, q.data(), t.data(), &summary, huber_a_);   // (0: cc_intrinsics_optimize_views)
+    last_status_ = cc_intrinsics_optimize_views_model(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+                                                      intr, frozen, q.data(), t.data(), &summary, huber_a_,
+                                                      static_cast<int32_t>(model_));   // (0, RadTan: cc_intrinsics_optimize_views)
     cc_last_call_timing(&last_timing_ms_[1]);
   }
   last_iterations_ = summary.iterations;
@@ -316,11 +321,7 @@ void Calibrator::Optimize(const std::vector<Points2D>& pixels_per_view, const st
   camera_matrix_(1, 1) = static_cast<float>(intr[FY]);
   camera_matrix_(0, 2) = static_cast<float>(intr[PX]);
   camera_matrix_(1, 2) = static_cast<float>(intr[PY]);
-  distortion_(0) = static_cast<float>(intr[K1]);
-  distortion_(1) = static_cast<float>(intr[K2]);
-  distortion_(2) = static_cast<float>(intr[P1]);
-  distortion_(3) = static_cast<float>(intr[P2]);
-  distortion_(4) = static_cast<float>(intr[K3]);
+  WriteBackDistortion(intr);
   last_timing_ms_[6] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
 }
 
@@ -329,7 +330,23 @@ void Calibrator::SetHuberLoss(const double a_pixels) {
   huber_a_ = a_pixels > 0.0 ? a_pixels : 0.0;
 }
 
+// slots K1.. of the solver's intrinsics -> distortion_: k1 k2 p1 p2 k3, or the fisheye model's four
+void Calibrator::WriteBackDistortion(const double* intr) {
+  const int n = model_ == CameraModel::Fisheye ? 4 : 5;
+  if (distortion_.size() != n) distortion_ = DynamicVector::Zero(n);
+  for (int i = 0; i < n; ++i) distortion_(i) = static_cast<float>(intr[K1 + i]);
+}
+
+void Calibrator::SetCameraModel(const CameraModel model) {
+  if (model != CameraModel::RadTan && model != CameraModel::Fisheye) throw std::invalid_argument("Calibrator::SetCameraModel: unknown model");
+  if (model == model_) return;
+  model_ = model;
+  distortion_ = DynamicVector::Zero(model == CameraModel::Fisheye ? 4 : 5);   // (the coefficients mean something else)
+}
+
 void Calibrator::ForceDistortionToConstant(const int coefficient) {
+  if (model_ == CameraModel::Fisheye && (coefficient < 0 || coefficient > 3))
+    throw std::invalid_argument("Calibrator::ForceDistortionToConstant: the fisheye model has the coefficients 0..3 (k1..k4)");
   frozen_intrinsics_.insert(coefficient + static_cast<int>(K1));
 }
 
@@ -345,7 +362,8 @@ Points2D Calibrator::Undistort(const Points2D& pixels) {
   flatten(camera_matrix_, distortion_, K9, d5);
   std::vector<float> in(pixels.size() * 2), out(pixels.size() * 2);
   for (size_t i = 0; i < pixels.size(); ++i) { in[2 * i] = pixels[i].x(); in[2 * i + 1] = pixels[i].y(); }
-  const int rc = cc_undistort(device_, K9, d5, (int64_t)pixels.size(), in.data(), out.data());
+  const int rc = model_ == CameraModel::Fisheye ? cc_undistort_fisheye(device_, K9, d5, (int64_t)pixels.size(), in.data(), out.data())
+                                                : cc_undistort(device_, K9, d5, (int64_t)pixels.size(), in.data(), out.data());
   if (rc != 0) throw std::runtime_error(std::string("Calibrator::Undistort: ") + cc_last_error());
   Points2D res;
   for (size_t i = 0; i < pixels.size(); ++i) res.emplace_back(out[2 * i], out[2 * i + 1]);
@@ -357,7 +375,8 @@ Points2D Calibrator::Distort(const Points2D& normalised) {
   flatten(camera_matrix_, distortion_, K9, d5);
   std::vector<float> in(normalised.size() * 2), out(normalised.size() * 2);
   for (size_t i = 0; i < normalised.size(); ++i) { in[2 * i] = normalised[i].x(); in[2 * i + 1] = normalised[i].y(); }
-  const int rc = cc_distort(device_, K9, d5, (int64_t)normalised.size(), in.data(), out.data());
+  const int rc = model_ == CameraModel::Fisheye ? cc_distort_fisheye(device_, K9, d5, (int64_t)normalised.size(), in.data(), out.data())
+                                                : cc_distort(device_, K9, d5, (int64_t)normalised.size(), in.data(), out.data());
   if (rc != 0) throw std::runtime_error(std::string("Calibrator::Distort: ") + cc_last_error());
   Points2D res;
   for (size_t i = 0; i < normalised.size(); ++i) res.emplace_back(out[2 * i], out[2 * i + 1]);

@@ -12,6 +12,9 @@ struct cc_summary;
 
 namespace calibrator {
 
+/// EXTENSION: the lens models of Calibrator::SetCameraModel (values of cc_solver.h's CC_MODEL_*)
+enum class CameraModel : int { RadTan = 0, Fisheye = 1 };
+
 class Calibrator {
  public:
   Calibrator(const int image_width, const int image_height);
@@ -68,6 +71,15 @@ class Calibrator {
   /// not exposed here (C ABI: cc_intrinsics_obs_cost).
   void SetHuberLoss(double a_pixels);
   double GetHuberLoss() const { return huber_a_; }
+  /// EXTENSION (the reference calibrates pinhole + radial-tangential distortion only): the lens model of Optimize / Estimate /
+  /// EstimateOpenCv / Distort / Undistort. Fisheye is the Kannala-Brandt / cv::fisheye model, theta_d = theta (1 + k1 theta^2 +
+  /// k2 theta^4 + k3 theta^6 + k4 theta^8) with theta the angle from the optical axis -- for lenses past ~100 degrees of field
+  /// of view. Switching the model resets the distortion to zeros of the model's length (5, or 4 for Fisheye);
+  /// ForceDistortionToConstant then takes 0..3. Estimate still starts from Zhang's pinhole initialisation with k = 0. Combines
+  /// with SetHuberLoss. Like the loss: ONE device, several kernels per LM iteration (LastSolverForm() == 0); Optimize / Estimate
+  /// throw std::invalid_argument when SetDevices selected several, EstimateMany when any calibrator is Fisheye.
+  void SetCameraModel(CameraModel model);
+  CameraModel GetCameraModel() const { return model_; }
   /// Status of the last Optimize: 0 or a negative cc_status. The reference has no error channel
   /// (ceres' summary is discarded), so Optimize itself never throws on solver failure.
   int LastStatus() const { return last_status_; }
@@ -95,6 +107,8 @@ class Calibrator {
   int image_h_;
   int device_{0};
   double huber_a_{0.0};
+  CameraModel model_{CameraModel::RadTan};
+  void WriteBackDistortion(const double* intr);
   std::vector<int> devices_;
   int last_status_{0};
   int last_iterations_{0};

@@ -929,6 +929,8 @@ __global__ __launch_bounds__(256) void k_intr_reset(IntrDev P, const double* ini
 
 // EXTENSION: the robust (Huber) form of the sweep and the per-observation cost kernel
 #include "cc_intrinsics_huber.hpp"
+// EXTENSION: the fisheye (Kannala-Brandt) camera model's sweep and per-observation cost kernel
+#include "cc_intrinsics_fisheye.hpp"
 
 // =============================================================================================
 // host side
@@ -964,6 +966,9 @@ struct cc_intrinsics : cc::SolveHost {   // pinned: a cached 512-byte block, hos
   uint32_t p_epoch = 0;         // last epoch handed to a launch (the seam words only ever see growing epochs)
   size_t p_box_bytes = 0;       // seam mailboxes (re-zeroed before the epochs wrap)
   double huber_a = 0.0;         // EXTENSION (cc_intrinsics_set_huber): > 0 -> HuberLoss(a), pixels; the handle then solves in the two-kernel form
+  int model = CC_MODEL_RADTAN;  // EXTENSION (cc_intrinsics_set_model): CC_MODEL_FISHEYE -> k_intr_sweep_fisheye, two-kernel form, one device
+  // the handle solves in the two-kernel form by choice, on one device (a loss or a model that only a sweep of its own carries)
+  bool own_sweep() const { return huber_a > 0.0 || model != CC_MODEL_RADTAN; }
 };
 
 namespace cc {
@@ -981,7 +986,9 @@ static void launch_sweep(cc_intrinsics* h, bool profile, int flags = 0) {
   // the index is there when the gather is issued: A/B at 1000 x 500, sweep 17.41 vs 17.42 us, iteration 42.50 vs 42.41 us,
   // and 2 KB per frame less traffic.
   flags |= 4;
-  if (h->huber_a > 0.0)
+  if (h->model == CC_MODEL_FISHEYE)
+    hipLaunchKernelGGL(k_intr_sweep_fisheye, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags, h->huber_a);
+  else if (h->huber_a > 0.0)
     hipLaunchKernelGGL(k_intr_sweep_huber, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags, h->huber_a);
   else
     hipLaunchKernelGGL(k_intr_sweep, dim3((unsigned)(h->F * h->d.T)), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d, flags);
@@ -1090,6 +1097,7 @@ int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const fl
 int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]) {
   using namespace cc;
   if (h && handle && h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_export: the handle has a Huber loss set (one device only)");
+  if (h && handle && h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_export: the handle has the fisheye model set (one device only)");
   if (int rc = exchange_export_begin(h, handle, "cc_intrinsics_exchange_export")) return rc;
   h->d.x = P2pDev{};
   return mailbox_export(&h->mailbox, kVecSolve, 16, handle);
@@ -1100,6 +1108,7 @@ int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks
   if (!h || !handles || rank < 0 || nranks < 1 || rank >= nranks || nranks > kP2pMaxRanks)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_exchange_attach: bad arguments (nranks must be 1..%d)", kP2pMaxRanks);
   if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: the handle has a Huber loss set (one device only)");
+  if (h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: the handle has the fisheye model set (one device only)");
   if (!h->mailbox.local) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: call cc_intrinsics_exchange_export first");
   if (h->comm) return fail(CC_ERR_STATE, "cc_intrinsics_exchange_attach: an RCCL communicator is already attached");
   CC_HIP(hipSetDevice(h->device));
@@ -1289,6 +1298,8 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
                              hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
   CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intr_sweep_huber),
                              hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
+  CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intr_sweep_fisheye),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
   return CC_OK;
 }
 }  // namespace cc
@@ -1329,6 +1340,7 @@ int cc_intrinsics_set_state(cc_intrinsics* h, const double* intr9, uint32_t mask
   }
   double k[16] = {0};
   for (int i = 0; i < 9; ++i) k[i] = intr9[i];
+  if (h->model == CC_MODEL_FISHEYE) { k[8] = 0.0; mask |= 1u << 8; }   // EXTENSION: slot 8 is unused by the fisheye model: held, and 0
   CC_HIP(hipStreamSynchronize(h->stream));
   CC_HIP(hipMemcpy(h->init_intr, k, sizeof(k), hipMemcpyHostToDevice));
   CC_HIP(hipMemcpy(h->init_pose, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -1421,6 +1433,23 @@ int cc_intrinsics_set_huber(cc_intrinsics* h, double a_pixels) {
   return CC_OK;
 }
 
+// EXTENSION: the camera model of later set_state / eval / solve / obs_cost calls (cc_intrinsics_fisheye.hpp). The slots of the
+// state mean something else under another model, so a change drops the state: cc_intrinsics_set_state comes next.
+int cc_intrinsics_set_model(cc_intrinsics* h, int32_t model) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_model: NULL handle");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_model: unknown model %d", (int)model);
+  if (model != CC_MODEL_RADTAN && (h->exchange || h->comm || h->mailbox.local))
+    return fail(CC_ERR_STATE, "cc_intrinsics_set_model: the handle has an exchange or a communicator attached (the fisheye model is for one device only)");
+  if (model == h->model) return CC_OK;
+  drop_graphs(h);   // kernel and arguments are baked into the graphs
+  h->model = model;
+  h->have_state = false;
+  return CC_OK;
+}
+
+int32_t cc_intrinsics_get_model(cc_intrinsics* h) { return h ? h->model : CC_MODEL_RADTAN; }
+
 // EXTENSION: the cost of every observation at the current point, in the caller's order: 1/2 rho(s) with the loss on, 1/2 s without.
 int cc_intrinsics_obs_cost(cc_intrinsics* h, double* obs_cost) {
   using namespace cc;
@@ -1434,7 +1463,10 @@ int cc_intrinsics_obs_cost(cc_intrinsics* h, double* obs_cost) {
   if (cost_blocks > (int64_t)INT32_MAX) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_obs_cost: %lld observations exceed the launch grid", (long long)h->N);
   double* d_out = nullptr;
   CC_HIP(hipMalloc(&d_out, (size_t)h->N * sizeof(double)));
-  hipLaunchKernelGGL(k_intr_obs_cost, dim3((unsigned)cost_blocks), dim3(256), 0, h->stream, h->d, st.cur & 1, h->huber_a, d_out);
+  if (h->model == CC_MODEL_FISHEYE)
+    hipLaunchKernelGGL(k_intr_obs_cost_fisheye, dim3((unsigned)cost_blocks), dim3(256), 0, h->stream, h->d, st.cur & 1, h->huber_a, d_out);
+  else
+    hipLaunchKernelGGL(k_intr_obs_cost, dim3((unsigned)cost_blocks), dim3(256), 0, h->stream, h->d, st.cur & 1, h->huber_a, d_out);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(obs_cost, d_out, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -1531,7 +1563,7 @@ static int solve_wait(cc_intrinsics* h, SolveRun* r) {
 // The whole solve as one launch of the persistent kernel. Starts from buffer 0 (solve_begin moved a continued solve's
 // accepted point there) or, after set_state / reset, from the initial-state arrays.
 static bool use_persistent(const cc_intrinsics* h, const SolveRun* r) {
-  return !h->comm && !r->profile && !(h->huber_a > 0.0) && (h->exchange ? h->persist_x_ok : h->persist_ok);
+  return !h->comm && !r->profile && !h->own_sweep() && (h->exchange ? h->persist_x_ok : h->persist_ok);
 }
 
 static int persistent_launch(cc_intrinsics* h, SolveRun* r) {
@@ -1739,7 +1771,7 @@ int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, i
 }
 
 int cc_intrinsics_solver_form(cc_intrinsics* h) {
-  if (!h || h->comm || h->huber_a > 0.0) return 0;   // (the robust sweep exists in the two-kernel form only)
+  if (!h || h->comm || h->own_sweep()) return 0;   // (the robust and the fisheye sweep exist in the two-kernel form only)
   return (h->exchange ? h->persist_x_ok : h->persist_ok) ? h->pq.teams : 0;
 }
 
@@ -1754,6 +1786,7 @@ int cc_intrinsics_profile_solve(cc_intrinsics* h, const cc_options* opt, int32_t
   if (!h || n < 1 || !avg_launch_ms) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_profile_solve: bad arguments");
   if (!h->have_state) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: no state set");
   if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: the handle has a Huber loss set and solves in the two-kernel form");
+  if (h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: the handle has the fisheye model set and solves in the two-kernel form");
   if (!h->persist_ok || h->comm || h->exchange) return fail(CC_ERR_STATE, "cc_intrinsics_profile_solve: the handle does not use the persistent form on a device of its own");
   CC_HIP(hipSetDevice(h->device));
   hipEvent_t e0, e1;
@@ -1931,7 +1964,8 @@ static int estimate_on_handle(cc_intrinsics* h, const ZhangScratch& zs, const cc
   if (K_init9) std::memcpy(K_init9, K9, sizeof(K9));
   // intrinsics order fx fy px py k1 k2 p1 p2 k3 (calibrator.cpp:168-179); the distortion starts from the caller's
   intr9[0] = K9[0]; intr9[1] = K9[4]; intr9[2] = K9[2]; intr9[3] = K9[5];
-  for (int i = 0; i < 5; ++i) intr9[4 + i] = distortion5 ? distortion5[i] : 0.0;
+  const int n_dist = h->model == CC_MODEL_FISHEYE ? 4 : 5;   // (fisheye: k1..k4, slot 8 unused)
+  for (int i = 0; i < 5; ++i) intr9[4 + i] = distortion5 && i < n_dist ? distortion5[i] : 0.0;
   for (size_t i = 0; i < qf.size(); ++i) q[i] = qf[i];
   for (size_t i = 0; i < tf.size(); ++i) t[i] = tf[i];
   if ((rc = cc_intrinsics_set_state(h, intr9, mask, q, t))) return rc;
@@ -2031,25 +2065,36 @@ struct ViewsUpload {
 };
 }  // namespace cc
 
-// (cc_intrinsics_estimate_views is this with huber_a = 0: the same path, bit for bit)
-int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+// (cc_intrinsics_estimate_views is this with huber_a = 0 and model 0: the same path, bit for bit. With the fisheye model the
+// start is still Zhang's pinhole one with k = 0, and `distortion5` holds the model's four coefficients.)
+int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
                                        const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a) {
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
   cc::last_call_status_reset();
   using namespace cc;
   if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views: needs >= 3 views and non-NULL arrays");
   if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_huber: huber_a is NaN");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_model: unknown model %d", (int)model);
+  if (model != CC_MODEL_RADTAN)   // (a missing device is reported as such, ahead of the pinned staging block that needs one)
+    if (int rc = select_device(device)) return rc;
   const ZhangScratch zs(F);
   double* tm = last_timing();
   for (int i = 0; i < 5; ++i) tm[i] = 0.0;
   ViewsUpload up;
   if (int rc = up.open("cc_intrinsics_estimate_views", device, F, uv_views, xyz_views, counts, 4, zs.bytes)) return rc;
   if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
+  up.h->model = model;
   const auto t0 = std::chrono::steady_clock::now();
   const int rc = estimate_on_handle(up.h, zs, opt, F, distortion5, mask, K_init9, intr9, q, t, summary, t0);
   if (rc) (void)hipStreamSynchronize(up.h->stream);   // (an early return may have left copies from the staging block in flight)
   return rc;
+}
+
+int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a) {
+  return cc_intrinsics_estimate_views_model(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, huber_a, CC_MODEL_RADTAN);
 }
 
 int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
@@ -2059,20 +2104,24 @@ int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t 
 }
 
 // cc_intrinsics_optimize for views given as separate arrays (Calibrator::Optimize's arguments, calibrator.cpp:70-74).
-// (cc_intrinsics_optimize_views is this with huber_a = 0: the same path, bit for bit)
-int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+// (cc_intrinsics_optimize_views is this with huber_a = 0 and model 0: the same path, bit for bit)
+int cc_intrinsics_optimize_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
                                        const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
-                                       double* q, double* t, cc_summary* summary, double huber_a) {
+                                       double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
   cc::last_call_status_reset();
   using namespace cc;
   if (F < 1 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views: needs >= 1 view and non-NULL arrays");
   if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_huber: huber_a is NaN");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_model: unknown model %d", (int)model);
+  if (model != CC_MODEL_RADTAN)   // (a missing device is reported as such, ahead of the pinned staging block that needs one)
+    if (int rc = select_device(device)) return rc;
   double* tm = last_timing();
   for (int i = 0; i < 5; ++i) tm[i] = 0.0;
   ViewsUpload up;
   if (int rc = up.open("cc_intrinsics_optimize_views", device, F, uv_views, xyz_views, counts, 0, 0)) return rc;
   if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
+  up.h->model = model;
   auto t0 = std::chrono::steady_clock::now();
   int rc = CC_OK;
   if (hipStreamSynchronize(up.h->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(CC_ERR_HIP, "upload failed"); }
@@ -2088,6 +2137,12 @@ int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, in
   return rc;
 }
 
+int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                       double* q, double* t, cc_summary* summary, double huber_a) {
+  return cc_intrinsics_optimize_views_model(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, huber_a, CC_MODEL_RADTAN);
+}
+
 int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
                                  const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
                                  double* q, double* t, cc_summary* summary) {
@@ -2099,6 +2154,7 @@ int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t ran
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_comm_init: bad arguments (nranks must be 1..32)");
   if (h->huber_a > 0.0) return fail(CC_ERR_STATE, "cc_intrinsics_comm_init: the handle has a Huber loss set (one device only)");
+  if (h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_intrinsics_comm_init: the handle has the fisheye model set (one device only)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
   drop_graphs(h);

@@ -1,0 +1,326 @@
+// cc_intrinsics_fisheye.hpp -- EXTENSION (the reference calibrates one lens model, pinhole + radial-tangential distortion,
+// calibrator.cpp:70-95): the Kannala-Brandt / OpenCV `fisheye` model for the single-camera intrinsics solve (gfx950).
+//
+//   (xc, yc, zc) = R(q) X + t,  rho = sqrt(xc^2 + yc^2),  theta = atan2(rho, zc),
+//   theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+//   u = fx theta_d xc / rho + px,  v = fy theta_d yc / rho + py          (residuals in pixels)
+//
+// Slots [fx fy px py k1 k2 k3 k4 -]: slot 8 is unused -- the host forces its bit of the constant mask and stores 0 in it, its
+// column of the rows is zero. For zc > 0 theta is OpenCV's atan(r); for zc <= 0 it stays finite and smooth, so a bad
+// intermediate pose does not poison the solve through a division by zc.
+//
+// Everything behind the sweep consumes the per-frame 16 x 16 Gram block of [J_intr(9) J_pose(6) r] and the statistics row, so
+// nothing behind the sweep changes. Included by cc_intrinsics.hip behind cc_intrinsics_huber.hpp: k_intr_sweep_fisheye is
+// k_intr_sweep_huber (same prologue, tiles, staging, MFMA contraction, outputs and ST_COST channel) with the rows below;
+// huber_a <= 0 is the plain sum of squares (one kernel serves the loss on and off). k_intr_obs_cost_fisheye writes the
+// per-observation costs. Copies under names of their own: the tuned kernels keep their code objects.
+// Out of scope: the persistent per-solve kernel, the batch, every multi-GPU form, the rig path, a fisheye-aware initialisation.
+#pragma once
+#include "cc_common.hpp"
+#include "cc_device.hpp"
+#include "cc_intrinsics_dev.hpp"
+
+namespace cc {
+
+// ---------------------------------------------------------------------------------------------
+// Per-observation quantities shared by the u-row and the v-row. With w = theta^2, P(w) = 1 + k1 w + .. + k4 w^4,
+// Q = d theta_d / d theta = P + 2 w P'(w), g = theta_d / rho = (theta / rho) P, n^2 = rho^2 + zc^2 and the direction
+// (cx, cy) = (xc, yc) / rho of the point around the axis:
+//   xd = theta_d cx,                    d xd / d k_j = theta cx w^j,
+//   d xd / d xc = g + D cx^2,  d xd / d yc = D cx cy,  d xd / d zc = -Q xc / n^2,   D = Q zc / n^2 - g
+// (yd alike). Near the axis the two terms of D agree to rho^2 / zc^2, and the textbook form D / rho^2 times xc^2 divides the
+// rounding of that difference by rho^2. Here D only ever meets cx^2, cx cy, cy^2 <= 1: its rounding, a few ulps of g, stays
+// a few ulps of the g it is added to, for every rho > 0 -- no series and no threshold. theta / rho is a quotient of two
+// accurately rounded numbers (atan2 has no cancellation). What is left is rho = 0 itself, 0 / 0 in cx, cy and theta / rho:
+// there the direction is taken as 0 (D = 0 in the limit, any direction serves) and theta / rho as its limit 1 / zc.
+// ---------------------------------------------------------------------------------------------
+struct FishCommon {
+  double a0, a1, a2, ex, ey, w, xd, yd, dxx, dxy, dyy, dxz, dyz;
+};
+
+__device__ __forceinline__ void fisheye_common(const double* k, const double* R, const double* t,
+                                               double X0, double X1, double X2, FishCommon& c) {
+  c.a0 = R[0] * X0 + R[1] * X1 + R[2] * X2;
+  c.a1 = R[3] * X0 + R[4] * X1 + R[5] * X2;
+  c.a2 = R[6] * X0 + R[7] * X1 + R[8] * X2;
+  const double xc = c.a0 + t[0], yc = c.a1 + t[1], zc = c.a2 + t[2];
+  const double rho2 = xc * xc + yc * yc;
+  const double rho = sqrt(rho2);
+  const double th = atan2(rho, zc);
+  const bool off_axis = rho2 > 0.0;
+  const double ir = off_axis ? 1.0 / rho : 0.0;
+  const double cx = xc * ir, cy = yc * ir;
+  const double e = off_axis ? th * ir : 1.0 / zc;
+  c.w = th * th;
+  const double k1 = k[4], k2 = k[5], k3 = k[6], k4 = k[7];
+  const double P = 1.0 + c.w * (k1 + c.w * (k2 + c.w * (k3 + c.w * k4)));
+  const double Q = 1.0 + c.w * (3.0 * k1 + c.w * (5.0 * k2 + c.w * (7.0 * k3 + c.w * (9.0 * k4))));
+  const double g = e * P;
+  const double qz = Q / (rho2 + zc * zc);
+  const double D = qz * zc - g;
+  c.ex = th * cx;
+  c.ey = th * cy;
+  c.xd = c.ex * P;
+  c.yd = c.ey * P;
+  const double Dx = D * cx;
+  c.dxx = g + Dx * cx;
+  c.dxy = Dx * cy;
+  c.dyy = g + D * cy * cy;
+  c.dxz = -qz * xc;
+  c.dyz = -qz * yc;
+}
+
+// the pose columns and the residual behind a row's first nine entries: b = d r / d (xc, yc, zc)
+__device__ __forceinline__ void fisheye_row_tail(const FishCommon& c, double b0, double b1, double b2, double rw, double* v) {
+  v[9] = 2.0 * (b2 * c.a1 - b1 * c.a2); v[10] = 2.0 * (b0 * c.a2 - b2 * c.a0); v[11] = 2.0 * (b1 * c.a0 - b0 * c.a1);
+  v[12] = b0; v[13] = b1; v[14] = b2; v[15] = rw;
+}
+
+// row of the u residual: d (fx xd + px - u) / d [fx fy px py k1 k2 k3 k4 - | rot(3) t(3)], then r; the weight wt (the Huber
+// weight, or 0 on a lane beyond the frame's last observation) rides on the row's factors as in row_u
+__device__ __forceinline__ void fisheye_row_u(const double* k, const FishCommon& c, double r, double* v, double wt) {
+  const double fx = k[0] * wt;
+  v[0] = c.xd * wt; v[1] = 0.0; v[2] = wt; v[3] = 0.0;
+  const double f1 = fx * c.ex * c.w, f2 = f1 * c.w, f3 = f2 * c.w;
+  v[4] = f1; v[5] = f2; v[6] = f3; v[7] = f3 * c.w; v[8] = 0.0;
+  fisheye_row_tail(c, fx * c.dxx, fx * c.dxy, fx * c.dxz, r * wt, v);
+}
+
+__device__ __forceinline__ void fisheye_row_v(const double* k, const FishCommon& c, double r, double* v, double wt) {
+  const double fy = k[1] * wt;
+  v[0] = 0.0; v[1] = c.yd * wt; v[2] = 0.0; v[3] = wt;
+  const double f1 = fy * c.ey * c.w, f2 = f1 * c.w, f3 = f2 * c.w;
+  v[4] = f1; v[5] = f2; v[6] = f3; v[7] = f3 * c.w; v[8] = 0.0;
+  fisheye_row_tail(c, fy * c.dxy, fy * c.dyy, fy * c.dyz, r * wt, v);
+}
+
+// ---------------------------------------------------------------------------------------------
+// fisheye sweep: k_intr_sweep_huber with the rows above. huber_a <= 0: weight 1 and rho = s -- the loss function runs with
+// a = +inf, where no observation is in the tail (rho = s and a weight of exactly 1), so the loss-off blocks ARE the blocks
+// of huber_a = +inf. sm layout and flags as in k_intr_sweep; sm[176..179] the waves' cost sums.
+// THREE waves per SIMD, not the four of k_intr_sweep: with the library's atan2 in the loop the kernel wants about 150 vector
+// registers (the scalar file is full at 106); at __launch_bounds__(256, 4) it spills 21 of them (88 bytes of scratch), at
+// (256, 3) it takes 168 and spills nothing. An arctangent of its own has not been tried. Measured: +12 % a round against the
+// radial-tangential sweep at 1000 x 500.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSweepThreads, 3) void k_intr_sweep_fisheye(IntrDev P, int flags, double huber_a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  double* s_stage = reinterpret_cast<double*>(smem_raw);       // [4][1024]
+  double* s_blk = s_stage;                                      // [1024] cross-wave reduce (after the loop)
+  double* sm = s_stage + 4 * kStageDoublesPerWave;              // [256] prologue scratch
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = P.T;
+  const int64_t f = (int64_t)blockIdx.x / T;
+  const int tile = (int)(blockIdx.x - f * T);
+  const bool in_solve = (flags & 1) != 0, restart = (flags & 2) != 0;
+  const LmCtl* ctl = P.ctl;
+  const int c_done = ctl->done, c_phase = ctl->phase, c_valid = ctl->step_valid, c_cur = ctl->cur;
+  const int done = restart ? 0 : c_done, phase = restart ? 0 : c_phase, step_valid = restart ? 0 : c_valid,
+            cur = restart ? 0 : c_cur;
+  int64_t s0 = P.off[f], s1 = P.off[f + 1];
+  if (T > 1) {   // this workgroup's tile of the frame
+    const int64_t len = (s1 - s0 + T - 1) / T;
+    s0 = s0 + tile * len < s1 ? s0 + tile * len : s1;
+    s1 = s0 + len < s1 ? s0 + len : s1;
+  }
+  const float2* uv2 = reinterpret_cast<const float2*>(P.uv);
+  const int64_t wrem = s1 - s0 - wave * 64;
+  const int npass = wrem > 0 ? (int)((wrem + kSweepThreads - 1) / kSweepThreads) : 0;   // passes of THIS wave
+  // unconditional loads from a clamped index (idle slots re-read a valid observation; the arena holds one slot even when N = 0)
+  const int64_t safe0 = s0 < P.N ? s0 : 0;
+  float2 nm;
+  float nX0, nX1, nX2;
+  {
+    const int64_t idx = s0 + tid;
+    const int64_t ic = idx < s1 ? idx : safe0;
+    nm = uv2[ic];
+    nX0 = P.xyz[ic * 3]; nX1 = P.xyz[ic * 3 + 1]; nX2 = P.xyz[ic * 3 + 2];
+  }
+  double gv;
+  {
+    const double* src;
+    if (tid < 60) src = P.Y + f * kYStride + tid;
+    else if (tid < 67) src = (restart ? P.init_pose : P.pose) + (size_t)f * 8 + (tid - 60);
+    else if (tid < 74) src = P.pose + ((size_t)P.F + f) * 8 + (tid - 67);
+    else if (tid < 83) src = (restart ? P.init_intr : P.intr) + (tid - 74);
+    else if (tid < 92) src = P.intr + 16 + (tid - 83);
+    else if (tid < 101) src = P.ds + (tid - 92);
+    else if (tid < 110) src = P.ss + (tid - 101);
+    else if (tid < 116) src = P.sp + f * 8 + (tid - 110);
+    else src = P.ss;   // (threads without a slot: any readable word)
+    gv = *src;
+  }
+  // previous Gram block of the frame (model-cost term): sum of its tiles, from the buffer of the accepted point
+  double g_old = 0.0;
+  if (tile == 0) {
+    const size_t base = cur ? (size_t)P.F : 0;
+    if (T == 1) g_old = P.blocks[(base + f) * 256 + tid];
+    else for (int k = 0; k < T; ++k) g_old += P.blocks[((base + f) * T + k) * 256 + tid];
+  }
+  if (tid < 116) sm[tid] = gv;
+  if (done) return;
+  if (phase != 0 && !step_valid) return;
+  if (P.x.on && in_solve && blockIdx.x == 0 && tid == 0) P.x.seq[1] += 1ull;   // (never with this model: kept so that the launch contract is k_intr_sweep's)
+  if (restart) {   // restore buffer 0 and clear the arrival counter of the elimination
+    if (tile == 0 && tid >= 60 && tid < 67) P.pose[(size_t)f * 8 + (tid - 60)] = sm[tid];
+    if (blockIdx.x == 0 && tid >= 74 && tid < 83) P.intr[tid - 74] = sm[tid];
+    if (blockIdx.x == 0 && tid == 0) *P.arrive = 0u;
+  }
+  const int dst = phase == 0 ? cur : (cur ^ 1);
+  __syncthreads();
+  const int pose_o = cur ? 67 : 60, intr_o = cur ? 83 : 74;
+  if (tid < 6) {
+    const double* Yr = sm + tid * 10;
+    double a = Yr[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) a += Yr[j] * sm[92 + j];
+    sm[129 + tid] = phase != 0 ? -a * sm[110 + tid] : 0.0;
+  } else if (tid >= 8 && tid < 17) {
+    const int j = tid - 8;
+    const double d = (phase == 0 || (P.mask & (1u << j))) ? 0.0 : sm[92 + j] * sm[101 + j];
+    sm[120 + j] = d;
+    const double kc = sm[intr_o + j] + d;
+    sm[148 + j] = kc;
+    if (blockIdx.x == 0 && phase != 0) P.intr[dst * 16 + j] = kc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double q[4], t[3], dp[6];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = sm[pose_o + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = sm[pose_o + 4 + i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) dp[i] = sm[129 + i];
+    double step2 = 0.0;
+    if (phase != 0) {
+      double qn[4];
+      quat_plus(q, dp, qn);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { const double d = qn[i] - q[i]; step2 += d * d; q[i] = qn[i]; }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { const double tn = t[i] + dp[3 + i]; const double d = tn - t[i]; step2 += d * d; t[i] = tn; }
+      if (tile == 0) {
+        double* pose_dst = P.pose + ((size_t)dst * P.F + f) * 8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pose_dst[i] = q[i];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) pose_dst[4 + i] = t[i];
+      }
+    }
+    double R[9];
+    quat_to_R(q, R);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) sm[136 + i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) sm[145 + i] = t[i];
+    sm[158] = step2;
+    sm[159] = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3] + t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
+  }
+  __syncthreads();
+
+  // model-cost term of this frame over the (scaled) block at the accepted point, reduced here and not behind the main loop
+  double qterm = 0.0;
+  if (phase != 0 && tile == 0) {
+    const int a = tid >> 4, b = tid & 15;
+    if (a < 15) qterm = b < 15 ? 0.5 * sm[120 + a] * g_old * sm[120 + b] : sm[120 + a] * g_old;
+  }
+  {
+    const double qw = wave_sum(qterm);
+    if (lane == 0) sm[170 + wave] = qw;
+  }
+
+  double R[9], tt[3], kk[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) R[i] = rfl(sm[136 + i]);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) tt[i] = rfl(sm[145 + i]);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) kk[i] = rfl(sm[148 + i]);
+  const uint32_t mask = P.mask;
+  const double a_loss = huber_a > 0.0 ? huber_a : __builtin_huge_val();   // (loss off: the loss whose tail nothing reaches)
+
+  // ---- main loop: 64 observations per wave per pass, no workgroup barrier. fisheye_common gives both residual components
+  // before the first row: the lane forms s, the weight of its two rows and its share of the cost
+  double* stage = s_stage + wave * kStageDoublesPerWave;
+  d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+  double hcost = 0.0;   // 1/2 sum rho over this lane's observations, in pass order
+  for (int p = 0; p < npass; ++p) {
+    const int64_t idx = s0 + (int64_t)p * kSweepThreads + tid;
+    const bool valid = idx < s1;  // only the last pass of a frame has idle lanes
+    const float2 m = nm;
+    const float X0 = nX0, X1 = nX1, X2 = nX2;
+    {   // next pass, unconditionally
+      const int64_t nidx = idx + kSweepThreads;
+      const int64_t ic = nidx < s1 ? nidx : safe0;
+      nm = uv2[ic];
+      nX0 = P.xyz[ic * 3]; nX1 = P.xyz[ic * 3 + 1]; nX2 = P.xyz[ic * 3 + 2];
+    }
+    FishCommon oc;
+    fisheye_common(kk, R, tt, (double)X0, (double)X1, (double)X2, oc);
+    const double ru = kk[0] * oc.xd + kk[2] - (double)m.x, rv = kk[1] * oc.yd + kk[3] - (double)m.y;
+    double rho, sr;
+    intr_huber(a_loss, ru * ru + rv * rv, rho, sr);
+    const double wrow = valid ? sr : 0.0;   // (an idle lane's rows are zero and it adds nothing to the cost)
+    hcost += valid ? 0.5 * rho : 0.0;
+    double v[16];
+    fisheye_row_u(kk, oc, ru, v, wrow);
+    stage_row(stage, lane, v);
+    wave_lds_fence();
+    gram_rows(stage, lane, acc0, acc1);
+    wave_lds_fence();
+    fisheye_row_v(kk, oc, rv, v, wrow);
+    stage_row(stage, lane, v);
+    wave_lds_fence();
+    gram_rows(stage, lane, acc0, acc1);
+    wave_lds_fence();
+  }
+  {
+    const double hw = wave_sum(hcost);
+    if (lane == 0) sm[176 + wave] = hw;
+  }
+
+  // ---- cross-wave reduction of the 16x16 block (C/D layout: col = lane & 15, row = (lane >> 4) + 4 * reg)
+  __syncthreads();  // s_blk aliases the staging buffers
+#pragma unroll
+  for (int r = 0; r < 4; ++r) s_blk[wave * 256 + ((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc0[r] + acc1[r];
+  __syncthreads();
+  const double g = gram_entry_held(mask, tid) ? 0.0 : (s_blk[tid] + s_blk[256 + tid]) + (s_blk[512 + tid] + s_blk[768 + tid]);
+  P.blocks[(((size_t)dst * P.F + f) * T + tile) * 256 + tid] = g;
+  if (tid == 255) {   // the thread that writes the row in k_intr_sweep; the cost is the waves' sum of 1/2 rho
+    double* st = P.stats + (size_t)blockIdx.x * kStatsCols;
+    st[ST_COST] = (sm[176] + sm[177]) + (sm[178] + sm[179]);
+    st[ST_QMODEL] = (sm[170] + sm[171]) + (sm[172] + sm[173]);
+    st[ST_STEP2] = tile == 0 ? sm[158] : 0.0;
+    st[ST_XNORM2] = tile == 0 ? sm[159] : 0.0;
+  }
+  if (phase == 0 && tid < 9 * 17 && tid % 17 == 0) P.hd0[(size_t)blockIdx.x * 16 + tid / 17] = g;
+}
+
+// ---------------------------------------------------------------------------------------------
+// per-observation cost at the point in buffer `cur`, in the caller's order, for the fisheye model: k_intr_obs_cost with the
+// model above (1/2 rho(s), or 1/2 s with huber_a <= 0). One lane per observation; exact square root.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_intr_obs_cost_fisheye(IntrDev P, int cur, double huber_a, double* out /*[N]*/) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P.N) return;
+  int64_t lo = 0, hi = P.F;   // the frame with off[lo] <= i < off[lo + 1] (empty frames share an offset: the last of them wins)
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (P.off[mid] <= i) lo = mid; else hi = mid;
+  }
+  const double* pose = P.pose + ((size_t)cur * P.F + lo) * 8;
+  const double* k = P.intr + cur * 16;
+  double kk[9], R[9];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) kk[j] = k[j];
+  const double q[4] = {pose[0], pose[1], pose[2], pose[3]}, t[3] = {pose[4], pose[5], pose[6]};
+  quat_to_R(q, R);
+  FishCommon oc;
+  fisheye_common(kk, R, t, (double)P.xyz[i * 3], (double)P.xyz[i * 3 + 1], (double)P.xyz[i * 3 + 2], oc);
+  const double ru = kk[0] * oc.xd + kk[2] - (double)P.uv[i * 2], rv = kk[1] * oc.yd + kk[3] - (double)P.uv[i * 2 + 1];
+  const double s = ru * ru + rv * rv, b = huber_a * huber_a;
+  out[i] = 0.5 * ((huber_a > 0.0 && s > b) ? 2.0 * huber_a * sqrt(s) - b : s);
+}
+
+}  // namespace cc

@@ -79,6 +79,71 @@ __global__ void k_undistort(PointParams P, int64_t n, const float2* __restrict__
   out[i] = make_float2((float)x, (float)y);
 }
 
+// EXTENSION: the fisheye (Kannala-Brandt) model's pair, cc_distort_fisheye / cc_undistort_fisheye (cc_solver.h). float in and
+// out, double arithmetic.
+struct FisheyePointParams {
+  double fx, fy, px, py, k1, k2, k3, k4;
+};
+
+__device__ __forceinline__ double fisheye_theta_d(const FisheyePointParams& P, double th) {
+  const double w = th * th;
+  return th * (1.0 + w * (P.k1 + w * (P.k2 + w * (P.k3 + w * P.k4))));
+}
+
+__global__ void k_distort_fisheye(FisheyePointParams P, int64_t n, const float2* __restrict__ xy, float2* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = xy[i].x, y = xy[i].y;
+  const double r = sqrt(x * x + y * y);
+  const double s = r > 0.0 ? fisheye_theta_d(P, atan(r)) / r : 1.0;   // (theta_d / r -> 1 on the axis)
+  out[i] = make_float2((float)(P.fx * (s * x) + P.px), (float)(P.fy * (s * y) + P.py));
+}
+
+// theta in [0, pi/2) with theta_d(theta) = td. f(theta) = theta_d(theta) - td has f(0) = -td <= 0: when f is positive at the
+// top of the interval (the largest double below pi/2) a root is bracketed, and Newton steps that leave the bracket or meet a
+// slope that is not positive fall back to bisection. When it is not (td beyond the polynomial's value there, or a polynomial
+// that turns back), plain Newton from theta = td climbs the first rising branch: it either converges inside the interval or
+// meets a slope <= 0 / leaves the interval / runs out of steps -- no root, NaN.
+__device__ __forceinline__ double fisheye_slope(const FisheyePointParams& P, double th) {
+  const double w = th * th;
+  return 1.0 + w * (3.0 * P.k1 + w * (5.0 * P.k2 + w * (7.0 * P.k3 + w * (9.0 * P.k4))));
+}
+
+__global__ void k_undistort_fisheye(FisheyePointParams P, int64_t n, const float2* __restrict__ uv, float2* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double x = ((double)uv[i].x - P.px) / P.fx, y = ((double)uv[i].y - P.py) / P.fy;
+  const double td = sqrt(x * x + y * y);
+  const float nanf_ = __builtin_nanf("");
+  if (!(td > 0.0)) {   // the axis itself (or a NaN input)
+    out[i] = td == 0.0 ? make_float2((float)x, (float)y) : make_float2(nanf_, nanf_);
+    return;
+  }
+  const double top = 1.5707963267948966;   // the double below pi/2 (pi/2 itself rounds down to it)
+  const bool bracketed = fisheye_theta_d(P, top) - td > 0.0;
+  double lo = 0.0, hi = top;
+  double th = td < top ? td : 0.5 * top;
+  bool found = false;
+  for (int it = 0; it < 200; ++it) {
+    const double f = fisheye_theta_d(P, th) - td;
+    const double fp = fisheye_slope(P, th);
+    if (f == 0.0) { found = true; break; }
+    double tn = th - f / fp;
+    if (bracketed) {
+      if (f > 0.0) hi = th; else lo = th;
+      if (!(fp > 0.0) || !(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
+    } else if (!(fp > 0.0) || !(tn >= 0.0 && tn <= top)) {
+      break;
+    }
+    const bool small = fabs(tn - th) <= 4.5e-16 * th;
+    th = tn;
+    if (small) { found = true; break; }
+  }
+  if (!found && !bracketed) { out[i] = make_float2(nanf_, nanf_); return; }
+  const double s = tan(th) / td;
+  out[i] = make_float2((float)(x * s), (float)(y * s));
+}
+
 static void inv3f(const float* m, float* o) {
   const float c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
   const float det = m[0] * c00 + m[1] * c01 + m[2] * c02;
@@ -88,15 +153,22 @@ static void inv3f(const float* m, float* o) {
   o[6] = c02 * id; o[7] = (m[1] * m[6] - m[0] * m[7]) * id; o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
-static int run_points(int device, const float* K, const float* dist, int64_t n, const float* in, float* out, bool undist) {
+// model 0: k_distort / k_undistort with dist5; model 1 (EXTENSION): the fisheye pair with dist4
+static int run_points(int device, const float* K, const float* dist, int64_t n, const float* in, float* out, bool undist, int model = 0) {
   if (n < 0 || n >= ((int64_t)1 << 39) || !K || !dist || (n > 0 && (!in || !out)))   // 32-bit launch grid of 256-thread blocks
     return fail(CC_ERR_BAD_ARGUMENT, "cc_(un)distort: bad arguments");
   if (int rc = select_device(device)) return rc;
   if (n == 0) return CC_OK;
-  PointParams P;
-  P.fx = K[0]; P.fy = K[4]; P.px = K[2]; P.py = K[5];
-  P.k1 = dist[0]; P.k2 = dist[1]; P.p1 = dist[2]; P.p2 = dist[3]; P.k3 = dist[4];
-  inv3f(K, P.Ki);
+  PointParams P{};
+  FisheyePointParams Q{};
+  if (model == 0) {
+    P.fx = K[0]; P.fy = K[4]; P.px = K[2]; P.py = K[5];
+    P.k1 = dist[0]; P.k2 = dist[1]; P.p1 = dist[2]; P.p2 = dist[3]; P.k3 = dist[4];
+    inv3f(K, P.Ki);
+  } else {
+    Q.fx = K[0]; Q.fy = K[4]; Q.px = K[2]; Q.py = K[5];
+    Q.k1 = dist[0]; Q.k2 = dist[1]; Q.k3 = dist[2]; Q.k4 = dist[3];
+  }
   // cached stream and cached scratch buffer (input | output): the Python workflow calls this once per frame
   // (cam_calibration.py:85-97), so the fixed cost matters more than the kernel
   hipStream_t stream = nullptr;
@@ -121,7 +193,9 @@ static int run_points(int device, const float* K, const float* dist, int64_t n, 
   CC_HIP(hipMemcpyAsync(din, in, (size_t)n * sizeof(float2), hipMemcpyHostToDevice, stream));
   const int threads = 256;
   const unsigned blocks = (unsigned)((n + threads - 1) / threads);
-  if (undist) hipLaunchKernelGGL(k_undistort, dim3(blocks), dim3(threads), 0, stream, P, n, din, dout);
+  if (model != 0 && undist) hipLaunchKernelGGL(k_undistort_fisheye, dim3(blocks), dim3(threads), 0, stream, Q, n, din, dout);
+  else if (model != 0) hipLaunchKernelGGL(k_distort_fisheye, dim3(blocks), dim3(threads), 0, stream, Q, n, din, dout);
+  else if (undist) hipLaunchKernelGGL(k_undistort, dim3(blocks), dim3(threads), 0, stream, P, n, din, dout);
   else hipLaunchKernelGGL(k_distort, dim3(blocks), dim3(threads), 0, stream, P, n, din, dout);
   CC_HIP(hipGetLastError());
   CC_HIP(hipMemcpyAsync(out, dout, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost, stream));
@@ -137,5 +211,11 @@ int cc_distort(int32_t device, const float* K9, const float* dist5, int64_t n, c
 }
 int cc_undistort(int32_t device, const float* K9, const float* dist5, int64_t n, const float* uv, float* xy_out) {
   return cc::run_points(device, K9, dist5, n, uv, xy_out, true);
+}
+int cc_distort_fisheye(int32_t device, const float* K9, const float* dist4, int64_t n, const float* xy, float* uv_out) {
+  return cc::run_points(device, K9, dist4, n, xy, uv_out, false, 1);
+}
+int cc_undistort_fisheye(int32_t device, const float* K9, const float* dist4, int64_t n, const float* uv, float* xy_out) {
+  return cc::run_points(device, K9, dist4, n, uv, xy_out, true, 1);
 }
 }

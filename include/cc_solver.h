@@ -286,6 +286,37 @@ int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, in
                                        cc_summary* summary, double huber_a);
 
 /* ---------------------------------------------------------------------------------------------
+ * EXTENSION (the reference calibrates one lens model, pinhole + radial-tangential distortion, calibrator.cpp:70-95): the
+ * Kannala-Brandt / OpenCV `fisheye` model for the single-camera solve, for lenses past ~100 degrees of field of view where the
+ * polynomial in r = tan(theta) diverges. For a point (xc, yc, zc) = R(q) X + t in the camera frame:
+ *   rho = sqrt(xc^2 + yc^2), theta = atan2(rho, zc), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *   u = fx theta_d xc / rho + px, v = fy theta_d yc / rho + py        (residuals in pixels; the limit value on the axis)
+ * For zc > 0 this is cv::fisheye's atan(r); for zc <= 0 it stays finite and smooth. Slots of intr9: fx fy px py k1 k2 k3 k4 -;
+ * slot 8 is unused: its bit of the constant mask is forced on and it reads back as 0.
+ * Out of scope: the persistent per-solve kernel, the batch (cc_intrinsics_batch_*), every multi-GPU form, cc_rigk_*, a
+ * fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K and poses with k = 0), other
+ * models.
+ * ------------------------------------------------------------------------------------------- */
+enum { CC_MODEL_RADTAN = 0, CC_MODEL_FISHEYE = 1 };
+/* The model of later cc_intrinsics_set_state / _eval / _solve / _reset / _get_state / _obs_cost calls; combines with
+ * cc_intrinsics_set_huber. A fisheye handle solves in the two-kernel form by choice, like a handle with the loss on
+ * (cc_intrinsics_solver_form reports 0; no give-up, no device back-off entry); cc_intrinsics_exchange_export / _attach,
+ * cc_intrinsics_comm_init and cc_intrinsics_profile_solve return CC_ERR_STATE on it, and so does this call on a handle with an
+ * exchange or communicator attached. A CHANGE of the model drops captured graphs and the state (the slots mean something
+ * else): call cc_intrinsics_set_state next. Unknown model: CC_ERR_BAD_ARGUMENT. */
+int cc_intrinsics_set_model(cc_intrinsics* h, int32_t model);
+int32_t cc_intrinsics_get_model(cc_intrinsics* h);
+/* The *_huber one-shot forms with a trailing model (those two ARE these with CC_MODEL_RADTAN). Fisheye: `distortion5` holds
+ * four values, k1..k4. */
+int cc_intrinsics_optimize_views_model(const cc_options* opt, int32_t device, int64_t n_frames, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t const_mask,
+                                       double* q_wxyz, double* t_xyz, cc_summary* summary, double huber_a, int32_t model);
+int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, int64_t n_frames, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5,
+                                       uint32_t const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summary, double huber_a, int32_t model);
+
+/* ---------------------------------------------------------------------------------------------
  * EXTENSION (nothing in the reference does it): a BATCH of independent single-camera problems solved together on one
  * device -- a rig's cameras before the rig solve (system_calibration.py runs optimize_intrinsics camera by camera,
  * cam_calibration.py:290-314), leave-one-view-out and bootstrap runs, subset fits. Problem p owns frames
@@ -508,6 +539,15 @@ int cc_distort(int32_t device, const float* K9, const float* dist5, int64_t n,
 /* Calibrator::Undistort (calibrator.cpp:118-155): pixel -> undistorted normalised coordinates. */
 int cc_undistort(int32_t device, const float* K9, const float* dist5, int64_t n, const float* uv,
                  float* xy_out);
+/* EXTENSION: the same pair for the fisheye model (CC_MODEL_FISHEYE above), dist4: k1 k2 k3 k4; float in and out, double
+ * arithmetic; K's fx fy px py are used. Distort: with r = |xy| and theta = atan(r), uv = K (theta_d / r) xy (the limit value at
+ * r = 0). Undistort: (x', y') = K^-1 uv, theta_d = |(x', y')|, the root theta in [0, pi/2) of theta_d(theta) by a bracketed
+ * Newton iteration, xy = tan(theta) / theta_d (x', y'). A pixel without a root in that interval (theta_d beyond the polynomial's
+ * range there, a non-monotone polynomial that never reaches it) gives NaN in both coordinates. */
+int cc_distort_fisheye(int32_t device, const float* K9, const float* dist4, int64_t n,
+                       const float* xy_normalized, float* uv_out);
+int cc_undistort_fisheye(int32_t device, const float* K9, const float* dist4, int64_t n, const float* uv,
+                         float* xy_out);
 
 #ifdef __cplusplus
 }
