@@ -1199,7 +1199,7 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   const size_t o_ipose = take((size_t)F * 8 * sizeof(double));
   // persistent kernel: frames per worker workgroup = the fewest (1, 2, 4) that still gives every frame a team of a resident
   // workgroup -- few frames spread over the chip (a 125-frame shard: one frame per compute unit), many share them four
-  // to a unit; seam mailboxes: one statistics row and one elimination row per worker workgroup, one row per leader
+  // to a unit; seam mailboxes: one statistics row and one elimination row per worker workgroup, one row of column totals
   int p_teams = 0;
   const bool want_persist = d.T == 1 && !(getenv("CC_INTR_PERSIST") && atoi(getenv("CC_INTR_PERSIST")) == 0);
   if (want_persist) {
@@ -1222,7 +1222,7 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   const size_t o_sbox = take(pgn * 2 * kPStatCols * sizeof(unsigned long long));
   const size_t o_pbox = take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
   const size_t o_rbox = take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
-  const size_t o_lbox = take(((pgn + kPLeaderRows - 1) / kPLeaderRows) * 2 * kPartialCols * sizeof(unsigned long long));
+  const size_t o_lbox = take((size_t)2 * kPartialCols * sizeof(unsigned long long));
   const size_t o_xbox = take(kPBcastWords * sizeof(unsigned long long));
   const size_t o_pfail = take(64);
   h->p_box_bytes = cursor - o_pbox0;

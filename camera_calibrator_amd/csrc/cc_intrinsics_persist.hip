@@ -12,10 +12,12 @@
 //             the observations (20 B each) are the only thing re-read every round (L2 / Infinity-Cache resident).
 //             Round: back-substitute the pose step, Plus, sweep (the same LDS-staged v_mfma_f64_16x16x4_f64 Gram
 //             as k_intr_sweep) -> statistics row -> [seam 1] -> eliminate the pose block of the accepted point's
-//             Gram block (16 lanes, 6 x 6 Cholesky in registers) -> elimination row -> [seam 2].
+//             Gram block (16 lanes, 6 x 6 Cholesky in registers) -> elimination row -> [seam 2]. Worker c mod G OWNS
+//             column c of the elimination rows: one wave pulls the column of all G rows (column-major boxes: one run of
+//             at most 4 KB), adds it up in the fixed order of cc_persist_sum.hpp and posts one total.
 //   control : owns the trust-region state (LmCtl), the log and the publication to the host. Seam 1: gathers the G
 //             statistics rows, takes the decision (lm_init / lm_decide), broadcasts {done, cur, radius (, Jacobi
-//             scales)}. Seam 2: gathers the G elimination rows, gradient / radius tests, 9 x 9 reduced solve with
+//             scales)}. Seam 2: gathers the eighty totals of the column owners, gradient / radius tests, 9 x 9 reduced solve with
 //             the matrix distributed by rows over nine lanes (v_readlane pivots), broadcasts {done, valid, step}.
 // Seams are self-validating 8-byte words {epoch32 : half of a double}, stored and polled with agent-scope (sc1)
 // accesses: an aligned 8-byte store is single-copy atomic, so there is no flag, no fence, no drain (MI355X guide,
@@ -25,6 +27,7 @@
 // everybody leaves, and a handle alone on its device runs the solve again with two kernels per iteration.
 #include "cc_intrinsics_persist.hpp"
 #include "cc_persist_dev.hpp"
+#include "cc_persist_sum.hpp"
 
 namespace cc {
 
@@ -55,7 +58,9 @@ static_assert(WG_X - WG_INTR >= 2 * 16 && WG_DS - WG_X >= 2 && WG_SS - WG_DS >= 
 
 // Control workgroup, all 1024 threads: column sums (maximum for column `maxcol`) of the G rows of a box whose words
 // carry `tag`. Thread -> (column, row group): rows grp, grp + NG, ... are polled BATCH at a time (all 2 BATCH loads in
-// flight, unconditional from clamped rows; BATCH = what sixteen rows need where there are never more) and added in that order; the NG group sums are then added in group order.
+// flight, unconditional from clamped rows) and added in that order; the NG group sums are then added in group order.
+// (The statistics rows of the first round come this way; the elimination rows came this way in two levels until the column owners
+// took them over -- cc_persist_sum.hpp keeps that order.)
 // out[0..ncols) valid for every thread after return. *s_ok (LDS) ends 0 when a row did not show up in time.
 template <int NC, int NG, int BATCH = 8>
 __device__ __forceinline__ void gather_rows(const u64* box, int G, unsigned tag, int ncols, int maxcol, double* s_part,
@@ -147,6 +152,106 @@ __device__ __forceinline__ void gather_stats4(const u64* box, int G, unsigned ta
 #pragma unroll
     for (int w = 0; w < THREADS / 64; ++w) a += s_part[w * 4 + tid];
     out[tid] = a;
+  }
+  __syncthreads();
+}
+
+// Word of (column c, worker g, low half) in an elimination box (pbox, rbox): column-major, so that an owner's column is one
+// contiguous run of G 16-byte pairs. (kPBoxColumnMajor = false: the row-major box, owners read at a 1280-byte stride.)
+__device__ __forceinline__ size_t persist_box_word(int c, int g, int G) {
+  return kPBoxColumnMajor ? ((size_t)c * (size_t)G + (size_t)g) * 2 : ((size_t)g * kPartialCols + (size_t)c) * 2;
+}
+
+// Worker w < kPartialCols, ONE wave: gathers the columns it owns -- w, w + G, ... -- of the G rows of `box` whose words carry
+// `tag`, adds each up in the order of cc_persist_sum.hpp and posts the totals into `obox`. Item i = (owned column i / G, row
+// i mod G) on lane i mod 64: at most 159 items with several columns, G <= kPMaxWorkers with one, so four pairs per lane, all
+// in flight at once, unconditional from clamped items. The values go through LDS (vals: kPMaxWorkers + kPartialCols + 2 kPSumRows
+// doubles: persist_sum_group reads sixteen values whatever the group holds) behind
+// fences of the wave alone: no workgroup barrier between the last arrival and the store of the total. Rows that did not
+// arrive: nothing is posted, the failure word is set, the control's own wait gives up and ends the solve -- as a failure.
+template <int NG>
+__device__ __forceinline__ void own_columns(const u64* box, u64* obox, int G, int w, unsigned tag, double* vals, unsigned* fail, int tid0, int tshift) {
+  constexpr int kPer = (kPMaxWorkers + 63) / 64;
+  int lane = tid0 & 63;   // (a fresh copy, as everywhere in the round loop: see the kernel)
+  asm volatile("" : "+v"(lane));
+  // (and a fresh copy of G: the reciprocal the divisions below go through is the same every round -- the compiler forms it in front
+  // of the round loop and, out of registers in the main loop, reloads it from scratch between the last arrival and the first addition)
+  asm volatile("" : "+s"(G));
+  const int nc = (kPartialCols - 1 - w) / G + 1, items = nc * G, nL = persist_sum_groups(G);
+  const u64* p[kPer];
+#pragma unroll
+  for (int u = 0; u < kPer; ++u) {
+    const int i = lane + 64 * u, ic = i < items ? i : 0, k = ic / G;
+    p[u] = box + persist_box_word(w + k * G, ic - k * G, G);
+  }
+  // (group sum t = (owned column t / nL, group t mod nL) on lane t mod 64, at most kPartialCols + 15 of them: two passes, whose
+  // indices are formed HERE, in front of the wait, not between the last arrival and the first addition)
+  int gv[2], gn[2], gm[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int t = lane + 64 * u, tc = t < nc * nL ? t : 0, k = tc / nL, j = tc - k * nL;
+    gv[u] = k * G + j * kPSumRows;
+    gn[u] = persist_sum_group_rows(G, j);
+    gm[u] = w + k * G == PC_GMAXP;
+  }
+  asm volatile("" : "+v"(gv[0]), "+v"(gv[1]), "+v"(gn[0]), "+v"(gn[1]), "+v"(gm[0]), "+v"(gm[1]));
+  u64 lo[kPer], hi[kPer];
+  bool good = true;
+  const long long t0 = wall_clock64();
+  for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+      lo[u] = ag_ld(p[u]);
+      hi[u] = ag_ld(p[u] + 1);
+    }
+    bool ok = true;
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) ok = ok && (unsigned)(lo[u] >> 32) == tag && (unsigned)(hi[u] >> 32) == tag;
+    if (ok) break;
+    if ((spins & 63u) == 63u && (timed_out(t0, tshift) || ag_ld32(fail) != 0u)) { good = false; break; }
+    __builtin_amdgcn_s_sleep(1);
+  }
+  if (__any(!good)) {
+    if (lane == 0) __hip_atomic_store(fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return;
+  }
+#pragma unroll
+  for (int u = 0; u < kPer; ++u)
+    if (lane + 64 * u < items) vals[lane + 64 * u] = ungranule(lo[u], hi[u]);
+  wave_lds_fence();
+  double* Ls = vals + kPMaxWorkers + kPSumRows;   // [nc][nL] group sums
+#pragma unroll
+  for (int u = 0; u < 2; ++u)
+    if (lane + 64 * u < nc * nL) Ls[lane + 64 * u] = persist_sum_group<NG>(vals + gv[u], gn[u], gm[u] != 0);
+  wave_lds_fence();
+  for (int k = lane; k < nc; k += 64) {
+    const int c = w + k * G;
+    const double total = persist_sum_group<NG>(Ls + k * nL, nL, c == PC_GMAXP);
+    ag_st(obox + 2 * c, granule(tag, total, 0));
+    ag_st(obox + 2 * c + 1, granule(tag, total, 1));
+  }
+}
+
+// Control workgroup: the kPartialCols totals of the column owners (one pair per thread, one round trip) -> out[0..kPartialCols).
+// *s_ok (LDS) ends 0 when a total did not show up in time.
+__device__ __forceinline__ void gather_totals(const u64* box, unsigned tag, double* out, unsigned* fail, int* s_ok, int tshift) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *s_ok = 1;
+  __syncthreads();
+  if (tid < kPartialCols) {
+    const u64* p = box + 2 * tid;
+    u64 lo, hi;
+    bool good = true;
+    const long long t0 = wall_clock64();
+    for (unsigned spins = 0;; ++spins) {
+      lo = ag_ld(p);
+      hi = ag_ld(p + 1);
+      if ((unsigned)(lo >> 32) == tag && (unsigned)(hi >> 32) == tag) break;
+      if ((spins & 63u) == 63u && (timed_out(t0, tshift) || ag_ld32(fail) != 0u)) { good = false; break; }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    out[tid] = ungranule(lo, hi);
+    if (!good) *s_ok = 0;
   }
   __syncthreads();
 }
@@ -264,8 +369,8 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
     }
     // ---- elimination rows (of the assumption, or of the second elimination after a miss) -> gradient tests, reduced solve
     const unsigned erow = hit ? e2 : e3;
-    // (the leaders among the workers have added the elimination rows sixteen at a time: one round trip here)
-    gather_rows<kPartialCols, THREADS / kPartialCols, (kPLeaderRows + THREADS / kPartialCols - 1) / (THREADS / kPartialCols)>(Q.lbox, (Q.G + kPLeaderRows - 1) / kPLeaderRows, erow, kPartialCols, PC_GMAXP, s_part, sv, Q.fail, s_int, (phase0 ? Q.first_shift : Q.timeout_shift));
+    // (the column owners among the workers have added the elimination rows up: eighty totals, one round trip here)
+    gather_totals(Q.lbox, erow, sv, Q.fail, s_int, (phase0 ? Q.first_shift : Q.timeout_shift));
     if (P.x.on) {
       // all-reduce of the 112 sums through the mailboxes (kind 0): the maximum of the pose gradients rides in a slot per rank
       if (tid >= kPartialCols && tid < kVecSolve) sv[tid] = 0.0;
@@ -639,7 +744,7 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
       }
     }
     // =========================== elimination of the frame's pose block at buffer cur_e under radius_e, the workgroup's
-    // row -> box (tag), and -- leaders -- the sum of sixteen rows -> lbox (tag)
+    // row -> box (tag), and -- column owners -- the total of each owned column -> lbox (tag)
     auto eliminate_and_post = [&](const int cur_e, const double radius_e, const bool first, u64* box, const unsigned tag) {
     CC_FRESH_TID(tid_e);
     if (has_frame && (tid_e & 255) >= sbase && (tid_e & 255) < sbase + 16) {
@@ -780,22 +885,13 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
             a = c == PC_GMAXP ? fmax(a, v) : a + v;
           }
         }
-        ag_st(box + (size_t)blockIdx.x * (2 * kPartialCols) + tid, granule(tag, a, tid & 1));
+        ag_st(box + persist_box_word(tid >> 1, (int)blockIdx.x, Q.G) + (tid & 1), granule(tag, a, tid & 1));
       }
     }
-    // ---- every sixteenth workgroup is a LEADER: it adds up the rows of its sixteen (it would only be waiting for the
-    // step otherwise) and posts ONE row for the control, which then reads G / 16 rows in a single round trip instead of G
-    if ((blockIdx.x % kPLeaderRows) == 0) {
-      int* s_lok = reinterpret_cast<int*>(s_wg + 250);
-      const int g0 = (int)blockIdx.x, n = Q.G - g0 < kPLeaderRows ? Q.G - g0 : kPLeaderRows;
-      double* lout = s_wg + 128;        // [80]; the group sums go through team 0's staging tiles (idle between sweeps)
-      gather_rows<kPartialCols, THREADS / kPartialCols, (kPLeaderRows + THREADS / kPartialCols - 1) / (THREADS / kPartialCols)>(box + (size_t)g0 * (2 * kPartialCols), n, tag, kPartialCols, PC_GMAXP, s_stage + 2048, lout,
-                                                        Q.fail, s_lok, (phase0 ? Q.first_shift : Q.timeout_shift));
-      CC_FRESH_TID(tid);
-      // (rows that did not arrive: nothing is posted, the control's own wait gives up and ends the solve -- as a failure)
-      if (!*s_lok && tid == 0) __hip_atomic_store(Q.fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (*s_lok && tid < 2 * kPartialCols) ag_st(Q.lbox + (size_t)(g0 / kPLeaderRows) * (2 * kPartialCols) + tid, granule(tag, lout[tid >> 1], tid & 1));
-    }
+    // ---- column `c` of the G rows is added up by its OWNER, worker c mod G (it would only be waiting for the step otherwise),
+    // on wave 3: idle here in every form, and polling from the moment the workgroup's own row has been issued
+    if (wave == 3 && (int)blockIdx.x < kPartialCols)
+      own_columns<THREADS / kPartialCols>(box, Q.lbox, Q.G, (int)blockIdx.x, tag, s_stage + 2048, Q.fail, tid0, (phase0 ? Q.first_shift : Q.timeout_shift));
     };
     // one wave waits for the control's broadcast `tag` (flags, radius, nine doubles) -> s_wg[WG_X ..]
     auto wait_bcast = [&](const unsigned tag) {

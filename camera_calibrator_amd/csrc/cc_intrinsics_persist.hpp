@@ -9,15 +9,15 @@ constexpr int kPMaxTeams = 4;                     // frames (teams of four waves
 constexpr int kPStatCols = 16;                    // doubles per statistics row (4 sums; + 9 diagonal sums in the first round)
 constexpr int kPBcastWords = 64;                  // words per broadcast box
 constexpr int kPMaxWorkers = 256;                 // worker workgroups: the control polls one statistics row per four of its 1024 threads (gather_stats4)
-constexpr int kPLeaderRows = 16;                  // elimination rows a leader workgroup adds up before the control sees them
+constexpr bool kPBoxColumnMajor = true;           // elimination boxes by column (an owner's column is one contiguous run) or by row
 
 // Seam mailboxes of one handle: self-validating 8-byte words {epoch32 : half of a double}, agent-scope stores and
 // loads (cc_intrinsics_persist.hip). Device memory, zeroed at creation; epochs only ever grow.
 struct PersistDev {
   unsigned long long* sbox;   // [G][2 * kPStatCols]   worker g's statistics row
-  unsigned long long* pbox;   // [G][2 * kPartialCols] worker g's elimination row (under the assumed decision)
-  unsigned long long* rbox;   // [G][2 * kPartialCols] ... of its second elimination in a round (after a decision the workers did not assume)
-  unsigned long long* lbox;   // [ceil(G / 16)][2 * kPartialCols] sum of sixteen elimination rows (by the leader among them)
+  unsigned long long* pbox;   // [kPartialCols][G] pairs: column c of worker g's elimination row (under the assumed decision)
+  unsigned long long* rbox;   // [kPartialCols][G] pairs: ... of its second elimination in a round (after a decision the workers did not assume)
+  unsigned long long* lbox;   // [kPartialCols] pairs: the columns' totals, each posted by its owner (worker c mod G)
   unsigned long long* xbox;   // [kPBcastWords] the control's broadcasts: flags, radius, nine doubles (step; Jacobi scales in the first round)
   unsigned* fail;             // [1] a wait inside the kernel timed out
   int32_t G;                  // worker workgroups; the control workgroup is block G

@@ -1,5 +1,5 @@
 """Where a round of the persistent intrinsics kernel goes: wall-clock marks (100 MHz, one counter for the chip) left in
-round CC_PERSIST_TIMING_ROUND by a worker workgroup in the middle of the grid (a leader) and by the control workgroup of a timing-only build
+round CC_PERSIST_TIMING_ROUND by a worker workgroup (the middle one, or the middle one of the column owners) and by the control workgroup of a timing-only build
 (scripts/build_variant.sh ptime cc_intrinsics_persist.hip --patch timing -DCC_PERSIST_TIMING; CC_LIB_PATH=scripts/ablate_build/libcc_ptime.so).
 Env F, M. Microseconds, median over solves; `t` = time since the worker's round start."""
 import ctypes as C, json, os, sys
@@ -30,17 +30,15 @@ for _ in range(15):
 prob.close()
 t = np.median(np.array(rows), axis=0)
 wn = ["round start", "pose step + Plus done", "main loop starts", "main loop done (this wave)", "all waves done", "block reduced, statistics",
-      "statistics row stored", "assumed elimination + row (+ leader sum) done", "elimination done", "elimination row stored",
-      "broadcast received (step if the assumption held)", "leader: sixteen rows gathered", "after a miss: step received",
+      "statistics row stored", "assumed elimination + row (+ owner's sum) done", "elimination done", "elimination row stored",
+      "broadcast received (step if the assumption held)", "owner: has its column", "after a miss: step received",
       "elimination: 6x6 factor done", "elimination: substitutions done", "broadcast: the poll set that matched was issued"]
-cn = ["waits for statistics rows", "rows gathered", "decision taken", "decision stored / skipped", "leader rows gathered", "solve done", "step stored",
+cn = ["waits for statistics rows", "rows gathered", "decision taken", "decision stored / skipped", "control has the totals", "solve done", "step stored",
       "solve: gradient maximum", "solve: rows built", "solve: factorisation + substitutions", "solve: tests, log record, flags"]
 sk = np.median(np.array(skews), axis=0)     # [G][4]: round start, statistics stored, elimination row stored, broadcast received
 names = ["round start", "statistics stored", "elimination row stored", "broadcast received"]
 print(json.dumps({"frames": F, "pts": M, "workgroups": G, "per_workgroup_marks_us": {n: {"min": round(float(sk[:, i].min()), 2), "median": round(float(np.median(sk[:, i])), 2),
       "max": round(float(sk[:, i].max()), 2)} for i, n in enumerate(names)}}))
-if t[27] > 0:   # (-DCC_PERSIST_PROBE_ALLGATHER: every worker also gathered the leaders' rows itself)
-    print(json.dumps({"probe": "all workers gather the leaders' rows", "middle worker's waves 1..3 had every row at (us)": [round(float(x), 2) for x in t[27:30]]}))
 print(json.dumps({"frames": F, "pts": M, "round_us": round(float(max(t[10], t[12])), 2),
-                  "worker": {n: round(float(t[i]), 2) for i, n in enumerate(wn) if t[i] > -1e6},
+                  "worker": {**{n: round(float(t[i]), 2) for i, n in enumerate(wn) if t[i] > -1e6}, "owner: total stored": round(float(t[27]), 2)},
                   "control": {n: round(float(t[16 + i]), 2) for i, n in enumerate(cn)}}))
