@@ -93,6 +93,7 @@ EXPORTED_SYMBOLS = [
     "cc_intrinsics_batch_set_huber", "cc_intrinsics_batch_estimate_huber",
     "cc_intrinsics_set_model", "cc_intrinsics_get_model", "cc_intrinsics_optimize_views_model", "cc_intrinsics_estimate_views_model",
     "cc_distort_fisheye", "cc_undistort_fisheye",
+    "cc_intrinsics_batch_set_model", "cc_intrinsics_batch_get_model", "cc_intrinsics_batch_estimate_model",
 ]
 # EXTENSION: camera models of the single-camera solve (cc_solver.h)
 MODEL_RADTAN, MODEL_FISHEYE = 0, 1
@@ -498,6 +499,18 @@ class IntrinsicsBatch:
         assert a.size == self.n_problems
         _check(lib().cc_intrinsics_batch_set_huber(self._h, _p(a, C.c_double)))
 
+    def set_model(self, model):
+        """EXTENSION: the camera model of the WHOLE batch in later set_state / solve / get_state calls
+        (cc_intrinsics_batch_set_model): MODEL_RADTAN (the default) or MODEL_FISHEYE (slots fx fy px py k1 k2 k3 k4 -, slot 8
+        held at 0 for every problem; one sweep per round for all problems, loss on or off). A change drops the state:
+        set_state comes next. The Huber thresholds stay."""
+        _check(lib().cc_intrinsics_batch_set_model(self._h, C.c_int32(model)))
+
+    def get_model(self):
+        model = C.c_int32(-1)
+        _check(lib().cc_intrinsics_batch_get_model(self._h, C.byref(model)))
+        return int(model.value)
+
     def get_state(self):
         """(intr [B][9], [q_p], [t_p]): the current point of every problem."""
         intr = np.zeros((self.n_problems, 9))
@@ -522,9 +535,20 @@ class IntrinsicsBatch:
         return [ss[p].iterations for p in range(self.n_problems)]
 
 
-def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=None, device=0, log_capacity=1024):
+def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=None, device=0, log_capacity=1024, model=0):
     """One-shot cc_intrinsics_batch_optimize. problems: one (frame_offsets, uv, xyz) per problem; intr [B][9]; q, t: one array
-    per problem. Returns (intr [B][9], [q_p], [t_p], [summary_p])."""
+    per problem. model != 0 (the extension, MODEL_FISHEYE for the whole batch): the same steps through a handle with
+    cc_intrinsics_batch_set_model in front of set_state. Returns (intr [B][9], [q_p], [t_p], [summary_p])."""
+    if model != 0:   # (0 is off: the one-shot symbol, below; an unknown value goes on to the C side, which refuses it)
+        h = IntrinsicsBatch(problems, device=device)
+        try:
+            h.set_model(model)
+            h.set_state(intr, q, t, const_mask)
+            ss = h.solve(options, log_capacity)
+            io, qs, ts = h.get_state()
+        finally:
+            h.close()
+        return io, qs, ts, ss
     poff, foff, uv, xyz = _batch_layout(problems)
     B = len(poff) - 1
     intr = _f64(np.asarray(intr, dtype=np.float64).reshape(-1)).copy()
@@ -541,19 +565,35 @@ def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=Non
     return intr.reshape(B, 9), qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]
 
 
-def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024, huber_a=None):
+def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024, huber_a=None,
+                              model=0):
     """cc_intrinsics_batch_estimate (Zhang initialisation per problem + the batched solve). distortion5: [B][5] or None;
     const_mask: one per problem or None; huber_a: one Huber threshold in pixels per problem (the extension
-    cc_intrinsics_batch_estimate_huber) or None. Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
+    cc_intrinsics_batch_estimate_huber) or None; model != 0: the extension cc_intrinsics_batch_estimate_model, one model for
+    the whole batch, huber_a passed on, `distortion5` then [B][4] (k1..k4) or [B][5] with the fifth entry ignored.
+    Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
     poff, foff, uv, xyz = _batch_layout(problems)
     B, F = len(poff) - 1, int(poff[-1])
     K = np.zeros((B, 9), dtype=np.float32)
     intr, q, t = np.zeros((B, 9)), np.zeros((F, 4)), np.zeros((F, 3))
+    if distortion5 is not None and model != 0:
+        d = np.asarray(distortion5, dtype=np.float64).reshape(B, -1)
+        distortion5 = np.concatenate([d[:, :4], np.zeros((B, 1))], axis=1)
     d5 = _f64(np.asarray(distortion5, dtype=np.float64).reshape(B, 5)) if distortion5 is not None else None
     mask = np.zeros(B, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
     opt = options if options is not None else default_options()
     ss, logs = _batch_summaries(B, log_capacity)
-    if huber_a is not None:
+    if model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
+        ha = None
+        if huber_a is not None:
+            ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
+            assert ha.size == B
+        _check(lib().cc_intrinsics_batch_estimate_model(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                                        _p(t, C.c_double), ss, _p(ha, C.c_double) if ha is not None else None,
+                                                        C.c_int32(model)))
+    elif huber_a is not None:
         ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
         assert ha.size == B
         _check(lib().cc_intrinsics_batch_estimate_huber(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),

@@ -173,6 +173,9 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
 // camera's bundle adjustment together, two launches per LM iteration for the whole set. Every calibrator brings its own constant set
 // and current distortion and gets K / distortion written back as float32 exactly as Estimate() does, plus its Last* fields. All of
 // them run on the first calibrator's device, in the two-kernel batched form (LastSolverForm() == 0).
+// The camera model belongs to the batch: all radial-tangential (cc_intrinsics_batch_estimate_huber, as before) or all fisheye
+// (cc_intrinsics_batch_estimate_model; four coefficients each, written back as Estimate() writes them). A mixture is refused --
+// the batch's one sweep kernel carries one model; a rig with both kinds of lens calls EstimateMany once per kind.
 void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
                               const std::vector<std::vector<Points3D>>& world_points) {
   const size_t B = calibrators.size();
@@ -195,6 +198,12 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
     poff[p + 1] = (int64_t)foff.size() - 1;
   }
   const size_t F = foff.size() - 1;
+  const CameraModel model = calibrators[0]->model_;
+  for (size_t p = 1; p < B; ++p)   // (refused before anything is packed)
+    if (calibrators[p]->model_ != model)
+      throw std::invalid_argument("Calibrator::EstimateMany: some calibrators have the fisheye model set (SetCameraModel) and some the "
+                                  "radial-tangential one; a batch has one model -- call EstimateMany once per model");
+  const bool fisheye = model == CameraModel::Fisheye;
   std::vector<float> uv(2 * n_obs + 2), xyz(3 * n_obs + 3);
   {
     size_t f = 0;
@@ -211,13 +220,10 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   std::vector<float> K9(9 * B);
   std::vector<double> huber(B, 0.0);   // every calibrator's own loss (SetHuberLoss); none set: the call without one
   bool any_huber = false;
-  for (size_t p = 0; p < B; ++p)   // (the batch carries the radial-tangential model only: refused before anything is packed for the device)
-    if (calibrators[p] && calibrators[p]->model_ != CameraModel::RadTan)
-      throw std::invalid_argument("Calibrator::EstimateMany: a calibrator has the fisheye model set (SetCameraModel); the batch is radial-tangential only");
   for (size_t p = 0; p < B; ++p) {
     huber[p] = calibrators[p]->huber_a_;
     any_huber = any_huber || huber[p] > 0.0;
-    for (int i = 0; i < 5; ++i) dist5[5 * p + i] = calibrators[p]->distortion_(i);
+    for (int i = 0; i < 5; ++i) dist5[5 * p + i] = i < calibrators[p]->distortion_.size() ? calibrators[p]->distortion_(i) : 0.0f;   // (fisheye: four coefficients)
     for (int idx : calibrators[p]->frozen_intrinsics_)
       if (idx >= 0 && idx < kNumIntrinsics) frozen[p] |= 1u << idx;
   }
@@ -225,9 +231,13 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
   std::vector<cc_summary> summaries(B);
   std::memset(summaries.data(), 0, B * sizeof(cc_summary));
-  const int rc = cc_intrinsics_batch_estimate_huber(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
-                                                    dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
-                                                    any_huber ? huber.data() : nullptr);
+  const int rc = fisheye
+      ? cc_intrinsics_batch_estimate_model(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
+                                           any_huber ? huber.data() : nullptr, CC_MODEL_FISHEYE)
+      : cc_intrinsics_batch_estimate_huber(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
+                                           any_huber ? huber.data() : nullptr);
   for (size_t p = 0; p < B; ++p) calibrators[p]->last_status_ = rc;
   // the same contract as Estimate(): environment errors and the Zhang preconditions throw, a solver-level status does not
   if (rc == CC_ERR_NO_DEVICE || rc == CC_ERR_HIP || rc == CC_ERR_COMM || rc == CC_ERR_BAD_ARGUMENT)
@@ -248,11 +258,15 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
     c.camera_matrix_(1, 1) = static_cast<float>(k[FY]);
     c.camera_matrix_(0, 2) = static_cast<float>(k[PX]);
     c.camera_matrix_(1, 2) = static_cast<float>(k[PY]);
-    c.distortion_(0) = static_cast<float>(k[K1]);
-    c.distortion_(1) = static_cast<float>(k[K2]);
-    c.distortion_(2) = static_cast<float>(k[P1]);
-    c.distortion_(3) = static_cast<float>(k[P2]);
-    c.distortion_(4) = static_cast<float>(k[K3]);
+    if (fisheye) {
+      c.WriteBackDistortion(k);   // (four coefficients, as Estimate() writes them)
+    } else {
+      c.distortion_(0) = static_cast<float>(k[K1]);
+      c.distortion_(1) = static_cast<float>(k[K2]);
+      c.distortion_(2) = static_cast<float>(k[P1]);
+      c.distortion_(3) = static_cast<float>(k[P2]);
+      c.distortion_(4) = static_cast<float>(k[K3]);
+    }
   }
 }
 

@@ -46,6 +46,9 @@ class Calibrator {
   /// together on the GPU (cc_intrinsics_batch_estimate: two launches per LM iteration for all of them). calibrators[i] is estimated
   /// from img_points[i] / world_points[i] with its own constant set and current distortion, and gets K, the distortion and its
   /// Last* fields exactly as its own Estimate() would set them (results equal to rounding). Runs on calibrators[0]'s device.
+  /// The camera model (SetCameraModel) belongs to the batch: all calibrators radial-tangential, or all Fisheye (each with its own
+  /// held coefficients 0..3, current k1..k4 and SetHuberLoss; cc_intrinsics_batch_estimate_model). A mixture throws
+  /// std::invalid_argument: a batch has one model, a rig with both kinds of lens calls EstimateMany once per kind.
   /// Throws std::invalid_argument when the three lists differ in length (or a camera's two lists, or a view's), and for the
   /// conditions Estimate() throws for.
   static void EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
@@ -77,7 +80,7 @@ class Calibrator {
   /// of view. Switching the model resets the distortion to zeros of the model's length (5, or 4 for Fisheye);
   /// ForceDistortionToConstant then takes 0..3. Estimate still starts from Zhang's pinhole initialisation with k = 0. Combines
   /// with SetHuberLoss. Like the loss: ONE device, several kernels per LM iteration (LastSolverForm() == 0); Optimize / Estimate
-  /// throw std::invalid_argument when SetDevices selected several, EstimateMany when any calibrator is Fisheye.
+  /// throw std::invalid_argument when SetDevices selected several, EstimateMany when its calibrators differ in their model.
   void SetCameraModel(CameraModel model);
   CameraModel GetCameraModel() const { return model_; }
   /// Status of the last Optimize: 0 or a negative cc_status. The reference has no error channel

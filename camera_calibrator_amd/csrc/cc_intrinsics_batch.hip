@@ -599,6 +599,7 @@ struct cc_intrinsics_batch {
   double* d_huber = nullptr;       // EXTENSION (cc_intrinsics_batch_set_huber): [B] HuberLoss(a) per problem, pixels; <= 0: off
   bool huber_on = false;           // ... on for at least one problem: the solve launches k_intrb_sweep_huber behind k_intrb_sweep
   bool huber_all = false;          // ... on for every problem: k_intrb_sweep has nothing to sweep and is left out
+  int model = CC_MODEL_RADTAN;     // EXTENSION (cc_intrinsics_batch_set_model): CC_MODEL_FISHEYE -> k_intrb_sweep_fisheye sweeps every problem
 };
 
 namespace cc {
@@ -681,6 +682,7 @@ static int batch_create_impl(cc_intrinsics_batch* h, const int64_t* frame_offset
   d.pad_ = 0;
   CC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_intrb_sweep), hipFuncAttributeMaxDynamicSharedMemorySize, kSweepLdsBytes));
   if (int rc = batch_sweep_huber_prepare()) return rc;
+  if (int rc = batch_sweep_fisheye_prepare()) return rc;
   return CC_OK;
 }
 
@@ -728,6 +730,11 @@ int cc_intrinsics_batch_set_state(cc_intrinsics_batch* h, const double* intr9, c
   batch_pack_state(h->B, h->Ftot, intr9, q, t, intr.data(), pose.data());
   std::vector<uint32_t> mask((size_t)h->B, 0u);
   if (const_mask) for (int64_t p = 0; p < h->B; ++p) mask[(size_t)p] = const_mask[p] & 0x1ffu;
+  if (h->model == CC_MODEL_FISHEYE)   // EXTENSION: slot 8 is unused by the fisheye model: held, and 0, for every problem
+    for (int64_t p = 0; p < h->B; ++p) {
+      intr[(size_t)p * 32 + 8] = intr[(size_t)p * 32 + 16 + 8] = 0.0;
+      mask[(size_t)p] |= 1u << 8;
+    }
   CC_HIP(hipStreamSynchronize(h->stream));
   CC_HIP(hipMemcpy(h->d.intr, intr.data(), intr.size() * sizeof(double), hipMemcpyHostToDevice));
   CC_HIP(hipMemcpy(h->d.pose, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice));   // buffer 0
@@ -756,6 +763,26 @@ int cc_intrinsics_batch_set_huber(cc_intrinsics_batch* h, const double* a_pixels
   CC_HIP(hipMemcpy(h->d_huber, a.data(), a.size() * sizeof(double), hipMemcpyHostToDevice));
   h->huber_on = on;
   h->huber_all = all;
+  return CC_OK;
+}
+
+// EXTENSION: the camera model of later set_state / solve / get_state calls (cc_intrinsics_fisheye.hpp), ONE for the whole batch.
+// The slots of the state mean something else under another model, so a change drops the state: cc_intrinsics_batch_set_state
+// comes next. The Huber thresholds stay. No device call.
+int cc_intrinsics_batch_set_model(cc_intrinsics_batch* h, int32_t model) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_set_model: NULL handle");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_set_model: unknown model %d", (int)model);
+  if (model == h->model) return CC_OK;
+  h->model = model;
+  h->have_state = false;
+  return CC_OK;
+}
+
+int cc_intrinsics_batch_get_model(const cc_intrinsics_batch* h, int32_t* model) {
+  using namespace cc;
+  if (!h || !model) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_get_model: NULL argument");
+  *model = h->model;
   return CC_OK;
 }
 
@@ -809,8 +836,13 @@ int cc_intrinsics_batch_solve(cc_intrinsics_batch* h, const cc_options* opt, cc_
     for (int i = 0; i < n; ++i) {
       // (EXTENSION, cc_intrinsics_batch_huber.hip: the problems with a Huber loss are swept again by the robust kernel, which
       // overwrites their blocks and statistics; the plain ones keep k_intrb_sweep's bits)
-      if (!h->huber_all) hipLaunchKernelGGL(k_intrb_sweep, dim3((unsigned)h->Ftot), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d);
-      if (h->huber_on) batch_sweep_huber_launch(h->d, h->d_huber, h->stream);
+      // (EXTENSION, cc_intrinsics_batch_fisheye.hip: a fisheye handle's one sweep serves every problem, loss on or off)
+      if (h->model == CC_MODEL_FISHEYE) {
+        batch_sweep_fisheye_launch(h->d, h->d_huber, h->stream);
+      } else {
+        if (!h->huber_all) hipLaunchKernelGGL(k_intrb_sweep, dim3((unsigned)h->Ftot), dim3(kSweepThreads), kSweepLdsBytes, h->stream, h->d);
+        if (h->huber_on) batch_sweep_huber_launch(h->d, h->d_huber, h->stream);
+      }
       hipLaunchKernelGGL(k_intrb_step, dim3((unsigned)B), dim3(256), 0, h->stream, h->d);
     }
     CC_HIP(hipGetLastError());
@@ -867,13 +899,17 @@ int cc_intrinsics_batch_optimize(const cc_options* opt, int32_t device, int64_t 
 // device arrays (zhang_on_device, same stream), its K and poses rounded to float as cc_intrinsics_estimate hands them
 // over, then the batched solve. distortion5 [B][5] (may be NULL: zeros), const_mask [B] (may be NULL), K_init9 [B][9] (may be NULL).
 // (huber_a [B] or NULL: EXTENSION, a Huber loss per problem; cc_intrinsics_batch_estimate is this with NULL -- the same path, bit for bit)
-int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+// (model: EXTENSION, the camera model of the whole batch; cc_intrinsics_batch_estimate_huber is this with CC_MODEL_RADTAN -- the
+// same path, bit for bit. With the fisheye model the start is still Zhang's pinhole K and poses, distortion5[p] holds k1..k4
+// and its fifth entry is ignored.)
+int cc_intrinsics_batch_estimate_model(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
                                        const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
                                        const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
-                                       const double* huber_a) {
+                                       const double* huber_a, int32_t model) {
   using namespace cc;
   const char* who = "cc_intrinsics_batch_estimate";
   if (!intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: intr9 / q / t are NULL", who);
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: unknown model %d", who, (int)model);
   if (huber_a)
     for (int64_t p = 0; p < n_problems; ++p)
       if (huber_a[p] != huber_a[p]) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a[%lld] is NaN", who, (long long)p);
@@ -891,6 +927,7 @@ int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, in
   cc_intrinsics_batch* h = nullptr;
   if (int rc = batch_create(who, device, n_problems, problem_offsets, frame_offsets, uv, xyz, per_frame, per_problem, false, &h)) return rc;
   struct Guard { cc_intrinsics_batch* h; ~Guard() { batch_destroy(h); } } guard{h};
+  h->model = model;   // (a fresh handle: no state yet)
   const size_t B = (size_t)h->B, F = (size_t)h->Ftot;
   double* dgram = reinterpret_cast<double*>(h->extra);
   float* dH = reinterpret_cast<float*>(h->extra + F * 256 * sizeof(double));
@@ -913,6 +950,7 @@ int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, in
     double* k = intr9 + p * 9;
     k[0] = K9[0]; k[1] = K9[4]; k[2] = K9[2]; k[3] = K9[5];
     for (int i = 0; i < 5; ++i) k[4 + i] = distortion5 ? distortion5[p * 5 + i] : 0.0;
+    if (model == CC_MODEL_FISHEYE) k[8] = 0.0;
   }
   for (size_t i = 0; i < qf.size(); ++i) q[i] = qf[i];
   for (size_t i = 0; i < tf.size(); ++i) t[i] = tf[i];
@@ -921,6 +959,14 @@ int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, in
   if (!rc) rc = cc_intrinsics_batch_solve(h, opt, summaries);
   if (!rc) rc = cc_intrinsics_batch_get_state(h, intr9, q, t);
   return rc;
+}
+
+int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
+                                       const double* huber_a) {
+  return cc_intrinsics_batch_estimate_model(opt, device, n_problems, problem_offsets, frame_offsets, uv, xyz, distortion5, const_mask,
+                                            K_init9, intr9, q, t, summaries, huber_a, CC_MODEL_RADTAN);
 }
 
 int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,

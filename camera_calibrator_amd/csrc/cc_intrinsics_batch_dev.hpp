@@ -1,5 +1,6 @@
-// cc_intrinsics_batch_dev.hpp -- what the two translation units of the batched intrinsics solve share: the device view of a
-// batch (cc_intrinsics_batch.hip, which owns it) and the interface of the robust form of its sweep (cc_intrinsics_batch_huber.hip).
+// cc_intrinsics_batch_dev.hpp -- what the translation units of the batched intrinsics solve share: the device view of a
+// batch (cc_intrinsics_batch.hip, which owns it) and the interfaces of the robust form of its sweep
+// (cc_intrinsics_batch_huber.hip) and of the fisheye model's sweep (cc_intrinsics_batch_fisheye.hip).
 #pragma once
 #include "cc_common.hpp"
 
@@ -34,5 +35,11 @@ struct IntrBatchDev {
 // and LDS as k_intrb_sweep.
 int batch_sweep_huber_prepare();   // once per handle, behind the device selection
 void batch_sweep_huber_launch(const IntrBatchDev& P, const double* huber_a, hipStream_t stream);
+
+// EXTENSION (cc_intrinsics_batch_fisheye.hip): the batch sweep of the fisheye model, for a handle whose model is
+// CC_MODEL_FISHEYE. It sweeps EVERY problem (huber_a[p] <= 0: the loss with a = +inf, weight exactly 1), so such a handle
+// launches it alone each round. Same grid, block and LDS as k_intrb_sweep.
+int batch_sweep_fisheye_prepare();   // once per handle, behind the device selection
+void batch_sweep_fisheye_launch(const IntrBatchDev& P, const double* huber_a, hipStream_t stream);
 
 }  // namespace cc

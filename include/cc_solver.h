@@ -293,9 +293,9 @@ int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, in
  *   u = fx theta_d xc / rho + px, v = fy theta_d yc / rho + py        (residuals in pixels; the limit value on the axis)
  * For zc > 0 this is cv::fisheye's atan(r); for zc <= 0 it stays finite and smooth. Slots of intr9: fx fy px py k1 k2 k3 k4 -;
  * slot 8 is unused: its bit of the constant mask is forced on and it reads back as 0.
- * Out of scope: the persistent per-solve kernel, the batch (cc_intrinsics_batch_*), every multi-GPU form, cc_rigk_*, a
- * fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K and poses with k = 0), other
- * models.
+ * The batch carries the model too (cc_intrinsics_batch_set_model below). Out of scope: the persistent per-solve kernel, every
+ * multi-GPU form, cc_rigk_*, a fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K
+ * and poses with k = 0), other models.
  * ------------------------------------------------------------------------------------------- */
 enum { CC_MODEL_RADTAN = 0, CC_MODEL_FISHEYE = 1 };
 /* The model of later cc_intrinsics_set_state / _eval / _solve / _reset / _get_state / _obs_cost calls; combines with
@@ -365,6 +365,25 @@ int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, in
                                        const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
                                        const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
                                        cc_summary* summaries, const double* huber_a);
+/* EXTENSION: the camera model of the batch (CC_MODEL_RADTAN, the default, or CC_MODEL_FISHEYE). The model belongs to the
+ * batch, not to a problem -- one handle, one model: a rig with both kinds of lens solves two batches. A fisheye handle
+ * launches ONE sweep per round for every problem, with the Huber loss on or off per problem (cc_intrinsics_batch_set_huber; a
+ * problem with the loss off, or with a threshold of +inf, keeps bit for bit what a batch without any loss returns for it);
+ * a radial-tangential handle launches exactly what it launched before. On a fisheye handle cc_intrinsics_batch_set_state
+ * takes the slots fx fy px py k1 k2 k3 k4 - per problem: bit 8 of every problem's constant mask is forced on, slot 8 is
+ * stored as 0 and reads back as 0. A CHANGE of the model drops the state (the slots mean something else): call
+ * cc_intrinsics_batch_set_state next, cc_intrinsics_batch_solve / _get_state return CC_ERR_STATE until then; setting the
+ * model the handle has changes nothing; the Huber thresholds survive either way. An unknown model or a NULL handle:
+ * CC_ERR_BAD_ARGUMENT, no device call. profile_kernels stays refused and use_graph ignored, as for every batch.
+ * cc_intrinsics_batch_estimate_model: cc_intrinsics_batch_estimate_huber with a trailing model (that one IS this with
+ * CC_MODEL_RADTAN). Fisheye: distortion5[p] holds k1..k4, its fifth entry is ignored; the start is Zhang's pinhole K and
+ * poses with the given coefficients, as in cc_intrinsics_estimate_views_model. */
+int cc_intrinsics_batch_set_model(cc_intrinsics_batch* h, int32_t model);
+int cc_intrinsics_batch_get_model(const cc_intrinsics_batch* h, int32_t* model);
+int cc_intrinsics_batch_estimate_model(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summaries, const double* huber_a, int32_t model);
 
 /* Contiguous frame partition balanced by observation count (host logic, no GPU needed).
  * first_frame has nranks+1 entries; rank r owns frames [first_frame[r], first_frame[r+1]). */
