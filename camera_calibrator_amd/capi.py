@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "cc_rig_create", "cc_rig_destroy", "cc_rig_set_state", "cc_rig_reset", "cc_rig_solve",
     "cc_rig_get_state", "cc_rig_solver_form", "cc_rig_solver_status", "cc_rig_eval", "cc_rig_optimize", "cc_rig_comm_init", "cc_rig_exchange_export", "cc_rig_exchange_attach", "cc_rigk_create",
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
-    "cc_rigk_get_camera_intrinsics", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
+    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
     "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
@@ -768,6 +768,17 @@ class RigProblem:
         intr9 = _f64(intr9)
         assert intr9.size == 9
         _check(lib().cc_rigk_set_camera_intrinsics(self._h, C.c_int64(camera), _p(intr9, C.c_double), C.c_uint32(const_mask)))
+
+    def set_model(self, model):
+        """The pixel model of every camera of a with_intrinsics handle (cc_rigk_set_model): MODEL_RADTAN (the default) or
+        MODEL_FISHEYE (slots fx fy px py k1 k2 k3 k4 -, slot 8 held at 0; tile form of the sweep, one device). A change drops
+        the intrinsics: set_intrinsics again before the next solve."""
+        _check(lib().cc_rigk_set_model(self._h, C.c_int32(model)))
+
+    def get_model(self):
+        out = C.c_int32(0)
+        _check(lib().cc_rigk_get_model(self._h, C.byref(out)))
+        return int(out.value)
 
     def get_camera_intrinsics(self, camera=None):
         """One camera's set, or (camera=None) an [n_cams, 9] array of all of them."""

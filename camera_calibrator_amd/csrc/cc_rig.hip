@@ -13,6 +13,7 @@
 //   k_rig_persist_w    the whole solve in one launch for rigs of at most four observed cameras (lean persistent form)
 //   k_rig_sweep_k2     extension (intrinsics): 16-column Gram on plain FMAs, two waves per group, compact records
 //   k_rig_sweep_adjk   extension, tiles (large rigs; CC_RIG_K_COMPACT=0)
+//   k_rig_sweep_adjk_fisheye   extension, tiles, the fisheye pixel model (cc_rigk_set_model; a unit of its own: cc_rig_fisheye.hip)
 // (The first formulation -- every row's 13 / 22 columns through the matrix pipe, k_rig_sweep -- lost to the adjoint forms in
 // round 2 and was deleted in round 5; git history has it.) Only cameras that are
 // observed AND not frozen own columns of the reduced system (any number of frozen / unobserved cameras
@@ -46,6 +47,7 @@
 #include "cc_persist_dev.hpp"
 #include "cc_rig_dev.hpp"
 #include "cc_rig_inner.hpp"
+#include "cc_rig_fisheye.hpp"
 
 namespace cc {
 
@@ -310,6 +312,7 @@ struct cc_rig : cc::SolveHost {   // pinned: host_pub = h_ctl's block, [20] fail
   bool frame_allowed = true; // poses-only, three-kernel path: the FRAME form of the sweep (k_rig_sweep_frame); CC_RIG_SWEEP_FRAME=0: one workgroup per group (k_rig_sweep_adj)
   int frame_waves = 2;       // waves per frame workgroup of the frame form
   int kmode = 0;
+  int model = CC_MODEL_RADTAN;   // cc_rigk_set_model: the pixel model of every camera of the handle (fisheye: cc_rig_fisheye.hpp, tiles only)
   std::vector<int64_t> perm;  // sorted position -> caller's observation index
   bool perm_inverse = false;   // columns: the storage holds int32 entries, [k] = where the caller's observation k went, counted from its frame's first position -- instead of perm[i] = caller's index of position i
   std::vector<std::pair<void*, size_t>> allocs;   // the chunks dev_alloc carves buffers from (cc::pool_alloc: recycled between handles)
@@ -505,7 +508,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     const double per_group = h->NG > 0 ? (double)h->N / (double)h->NG : 0.0;
     bool on = per_group >= 448.0;
     if (const char* e = getenv("CC_RIG_K_COMPACT")) on = atoi(e) != 0;
-    d.kcm = (kmode && !h->big && on) ? 1 : 0;
+    d.kcm = (kmode && !h->big && on && h->model != CC_MODEL_FISHEYE) ? 1 : 0;   // (no compact-record form of the fisheye sweep)
   }
   d.C = (int32_t)C; d.CO = CO; d.CK = CK; d.S = S; d.SW = S + 1;
   d.T = (d.SW + 15) / 16; d.nT = d.T * (d.T + 1) / 2; d.ZS = 16 * d.T + ((d.T & 1) ? 0 : 16);
@@ -785,6 +788,11 @@ static int rig_size_reduce_grid(cc_rig* h) {
   return 0;
 }
 
+static RigFishDev rig_fish_dev(const cc_rig* h) {
+  const RigDev& d = h->d;
+  return RigFishDev{d.F, d.NG, d.C, d.CK, d.uv, d.oxyz, d.widx, d.wxyz, d.goff, d.gframe, d.gcam, d.cam_fixed, d.kset, d.kmask, d.cam, d.pose,
+                    d.intr, d.camrec, d.frec, d.krec, d.gblocks, d.gstats, d.ghd0, d.ghdk, d.gcomp, d.ctl, d.gstride, d.huber_a, d.huber_b, d.huber_2a};
+}
 static RigInnerDev rig_inner_dev(const cc_rig* h) {
   const RigDev& d = h->d;
   return RigInnerDev{d.F, d.NG, d.C, d.fmode, d.uv, d.oxyz, d.goff, d.gframe, d.gcam, d.fgoff, d.cam_goff, d.cam_glist, d.pcol,
@@ -803,7 +811,8 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
   const RigDev& d = h->d;
   struct RoundCount { cc_rig* h; ~RoundCount() { h->enq_round++; } } count_round{h};
   auto sweep = [&]() {
-    if (d.kcm) hipLaunchKernelGGL(k_rig_sweep_k2, dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);   // (a workgroup of two waves per group)
+    if (h->model == CC_MODEL_FISHEYE) rig_fisheye_enqueue_sweep(rig_fish_dev(h), h->stream, h->sweep_waves);
+    else if (d.kcm) hipLaunchKernelGGL(k_rig_sweep_k2, dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);   // (a workgroup of two waves per group)
     else if (d.kmode && h->sweep_waves == 1) hipLaunchKernelGGL(k_rig_sweep_adjk<1>, dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
     else if (d.kmode) hipLaunchKernelGGL(k_rig_sweep_adjk<4>, dim3((unsigned)h->NG), dim3(256), 0, h->stream, d);
     else if (d.fmode) {
@@ -1295,7 +1304,8 @@ static int rigk_set(cc_rig* h, int64_t camera, const double* intr9, uint32_t con
   CC_HIP(hipStreamSynchronize(h->stream));
   double k16[16] = {0};
   for (int i = 0; i < 9; ++i) k16[i] = intr9[i];
-  const uint32_t m = const_mask & 0x1ffu;
+  uint32_t m = const_mask & 0x1ffu;
+  if (h->model == CC_MODEL_FISHEYE) { m |= 1u << 8; k16[8] = 0.0; }   // slot 8 is not part of the model: held, stored as 0 (cc_intrinsics_set_state)
   for (int s = 0; s < CK; ++s) {
     if (camera >= 0 && s != camera) continue;
     CC_HIP(hipMemcpy(h->init_intr + (size_t)s * 16, k16, sizeof(k16), hipMemcpyHostToDevice));
@@ -1326,6 +1336,30 @@ int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9) {
   return CC_OK;
 }
 int cc_rigk_get_intrinsics(cc_rig* h, double* intr9) { return cc_rigk_get_camera_intrinsics(h, 0, intr9); }
+
+// EXTENSION: the pixel model of the handle, for all of its cameras (one shared set or one per camera)
+int cc_rigk_set_model(cc_rig* h, int32_t model) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_model: NULL handle");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_model: unknown model %d", (int)model);
+  if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_set_model: the handle was created without intrinsics (cc_rig_create)");
+  if (model == h->model) return CC_OK;
+  if (model == CC_MODEL_FISHEYE && (h->comm || h->exchange || h->mailbox.local))
+    return fail(CC_ERR_STATE, "cc_rigk_set_model: the fisheye model runs on one device only (the handle has an exchange or a communicator attached)");
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  h->model = model;
+  h->have_intr = false;   // the slots mean something else: cc_rigk_set_intrinsics again
+  const std::vector<uint8_t> any = h->seen_any;
+  return rig_layout(h, any);   // (tile form for the fisheye model; drops the captured graphs)
+}
+int cc_rigk_get_model(cc_rig* h, int32_t* model) {
+  using namespace cc;
+  if (!h || !model) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_get_model: NULL argument");
+  if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_get_model: the handle was created without intrinsics (cc_rig_create)");
+  *model = h->model;
+  return CC_OK;
+}
 
 void cc_rig_destroy(cc_rig* h) {
   if (h) cc::last_call_status_record(h->ran_form >= 0 ? h->ran_form : cc_rig_solver_form(h), h->form_reruns, h->form_note);   // (what a one-shot call's caller can still ask for)
@@ -1748,7 +1782,8 @@ int cc_rig_get_state(cc_rig* h, double* cam_q, double* cam_t, double* frame_q, d
     }
   }
   if (obs_cost && h->N > 0) {
-    hipLaunchKernelGGL(k_rig_obs_cost, dim3((unsigned)h->NG), dim3(256), 0, h->stream, h->d, cur, h->d_cost);
+    if (h->model == CC_MODEL_FISHEYE) rig_fisheye_enqueue_obs_cost(rig_fish_dev(h), h->stream, cur, h->d_cost);
+    else hipLaunchKernelGGL(k_rig_obs_cost, dim3((unsigned)h->NG), dim3(256), 0, h->stream, h->d, cur, h->d_cost);
     CC_HIP(hipGetLastError());
     // through the cached pinned block (full PCIe rate, no fresh 8N-byte vector to fault in), back into the caller's order on
     // several host threads
@@ -1821,6 +1856,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
   using namespace cc;
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_comm_init: bad arguments (nranks must be 1..32)");
+  if (h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has the fisheye model (one device only: cc_rigk_set_model)");
   if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
@@ -1844,6 +1880,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
 
 int cc_rig_exchange_export(cc_rig* h, uint8_t handle[64]) {
   using namespace cc;
+  if (h && h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_exchange_export: the handle has the fisheye model (one device only: cc_rigk_set_model)");
   if (int rc = exchange_export_begin(h, handle, "cc_rig_exchange_export")) return rc;
   h->d.x = P2pDev{};
   int k0 = 0, k1 = 0;
@@ -1856,6 +1893,7 @@ int cc_rig_exchange_attach(cc_rig* h, int32_t rank, int32_t nranks, const uint8_
   using namespace cc;
   if (!h || !handles || rank < 0 || nranks < 1 || rank >= nranks || nranks > kP2pMaxRanks)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_attach: bad arguments (nranks must be 1..%d)", kP2pMaxRanks);
+  if (h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has the fisheye model (one device only: cc_rigk_set_model)");
   if (!h->mailbox.local) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: call cc_rig_exchange_export first");
   if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   if (h->comm) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: an RCCL communicator is already attached");

@@ -293,8 +293,9 @@ int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, in
  *   u = fx theta_d xc / rho + px, v = fy theta_d yc / rho + py        (residuals in pixels; the limit value on the axis)
  * For zc > 0 this is cv::fisheye's atan(r); for zc <= 0 it stays finite and smooth. Slots of intr9: fx fy px py k1 k2 k3 k4 -;
  * slot 8 is unused: its bit of the constant mask is forced on and it reads back as 0.
- * The batch carries the model too (cc_intrinsics_batch_set_model below). Out of scope: the persistent per-solve kernel, every
- * multi-GPU form, cc_rigk_*, a fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K
+ * The batch carries the model too (cc_intrinsics_batch_set_model below), and so does the rig solve with intrinsics
+ * (cc_rigk_set_model). Out of scope: the persistent per-solve kernel, every
+ * multi-GPU form, a fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K
  * and poses with k = 0), other models.
  * ------------------------------------------------------------------------------------------- */
 enum { CC_MODEL_RADTAN = 0, CC_MODEL_FISHEYE = 1 };
@@ -487,6 +488,19 @@ int cc_rigk_create_per_camera(int32_t device, int64_t n_cams, int64_t n_frames, 
                               double huber_a, cc_rig** out);
 int cc_rigk_set_camera_intrinsics(cc_rig* h, int64_t camera, const double* intr9, uint32_t const_mask);
 int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9);
+/* EXTENSION: the pixel model of a cc_rigk_* handle (CC_MODEL_RADTAN, the default, or CC_MODEL_FISHEYE, above). The model
+ * belongs to the handle, for all of its cameras -- one shared set or one per camera; a rig that mixes both is out of scope.
+ * Fisheye: the slots are fx fy px py k1 k2 k3 k4 -; cc_rigk_set_intrinsics / _set_camera_intrinsics force bit 8 of the
+ * constant mask and store 0 in slot 8. A CHANGE of the model drops the captured graphs and the intrinsics (the next solve
+ * needs cc_rigk_set_intrinsics again) and puts the handle on the tile form of the sweep (k_rig_sweep_adjk_fisheye: there is
+ * no compact-record form, whatever the group size and CC_RIG_K_COMPACT). Setting the model the handle has is a no-op; a
+ * handle that never leaves CC_MODEL_RADTAN launches the kernels it always did. Large rigs (<= 255 shared coordinates),
+ * cc_rig_eval / _reset / _solver_status and profiled rounds work as on any cc_rigk_* handle.
+ * CC_ERR_STATE: a poses-only handle (cc_rig_create); CC_MODEL_FISHEYE on a handle with an exchange or a communicator
+ * (and cc_rig_comm_init / cc_rig_exchange_export / _attach on a fisheye handle: one device only).
+ * CC_ERR_BAD_ARGUMENT: an unknown model. */
+int cc_rigk_set_model(cc_rig* h, int32_t model);
+int cc_rigk_get_model(cc_rig* h, int32_t* model);
 
 /* One-shot: the call ExtrinsicsCalibrator::Optimize makes in place of
  * extrinsics_calibrator.cpp:92-225. opt == NULL -> cc_options_init with max_iterations = 1000. */

@@ -14,12 +14,15 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ["cc_intrinsics.hip", "cc_intrinsics_batch.hip", "cc_intrinsics_batch_huber.hip", "cc_intrinsics_persist.hip", "cc_points.hip"]
+UNITS = ["cc_rig.hip", "cc_rig_inner.hip", "cc_rig_fisheye.hip", "cc_intrinsics.hip", "cc_intrinsics_batch_fisheye.hip", "cc_intrinsics_batch.hip", "cc_intrinsics_batch_huber.hip",
+         "cc_intrinsics_persist.hip", "cc_points.hip"]
 FLAGS = {"cc_points.hip": ["-ffp-contract=off"]}
 
 
 def assembly(tree, unit, out):
     src = os.path.join(tree, "camera_calibrator_amd", "csrc", unit)
+    if not os.path.exists(src):   # a unit one of the trees does not have yet: no kernels on that side
+        return ""
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-o", out, src]
                           + FLAGS.get(unit, []), stderr=subprocess.DEVNULL)
     return open(out).read()
