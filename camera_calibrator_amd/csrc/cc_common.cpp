@@ -69,7 +69,7 @@ void* pinned_block_get() {
     if (!g_pinned_free.empty()) { void* p = g_pinned_free.back(); g_pinned_free.pop_back(); return p; }
   }
   void* p = nullptr;
-  if (hipHostMalloc(&p, 512, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (hipHostMalloc(&p, kPinnedBlockBytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
   return p;
 }
 

@@ -32,8 +32,9 @@ int select_device(int device);
 
 // Small per-process caches of resources that are slow to create and destroy (hipHostMalloc/hipHostFree
 // ~0.2-0.4 ms, streams ~0.1 ms): a one-shot solve should not pay for them every time. Pinned blocks
-// are 512 bytes (control block / options staging); streams are per device. Thread-safe; entries live
-// until the process ends.
+// are kPinnedBlockBytes (control block / options staging in the first 512, the intrinsics handle's tagged publication
+// behind them: cc_persist_publish.hpp); streams are per device. Thread-safe; entries live until the process ends.
+constexpr size_t kPinnedBlockBytes = 1024;
 void* pinned_block_get();
 void pinned_block_put(void* p);
 int zhang_on_device(hipStream_t stream, int64_t F, const int64_t* doff, const float* duv, const float* dxyz,

@@ -937,7 +937,7 @@ __global__ __launch_bounds__(256) void k_intr_reset(IntrDev P, const double* ini
 // =============================================================================================
 #include "cc_solve_host.hpp"
 
-struct cc_intrinsics : cc::SolveHost {   // pinned: a cached 512-byte block, host_pub (160 B) | h_ctl | h_opts
+struct cc_intrinsics : cc::SolveHost {   // pinned: a cached block, host_pub (160 B) | h_ctl | h_opts in its first 512 bytes, the persistent solves' tagged words behind them
   cc::IntrDev d{};
   int64_t F = 0, N = 0;
   int elim_blocks = 1;
@@ -1046,6 +1046,11 @@ static int read_ctl(cc_intrinsics* h, LmCtl* c) {
 // the chunk just enqueued has published its control block (wait_published, cc_solve_host.hpp; no failure word, one stream)
 static int wait_chunk(cc_intrinsics* h, LmCtl* c) {
   return wait_published(h, nullptr, c, nullptr, "the solver", [=] { return read_ctl(h, c); });
+}
+
+// ... the persistent kernel's whole solve has (wait_published_tagged: tagged words, the same count)
+static int wait_solve(cc_intrinsics* h, LmCtl* c) {
+  return wait_published_tagged(h, c, "the solver", [=] { return read_ctl(h, c); });
 }
 
 }  // namespace cc
@@ -1275,6 +1280,9 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   h->h_ctl = reinterpret_cast<LmCtl*>(static_cast<char*>(h->pinned) + 192);
   h->h_opts = reinterpret_cast<LmOpts*>(static_cast<char*>(h->pinned) + 352);
   h->host_pub[0] = 0ull;     // a recycled block may carry an old sequence number; the device counter starts at 0
+  // (... and the tagged words of an earlier handle's solves, whose tags this handle's solves will carry again: no tag is 0)
+  static_assert((kPubTaggedAt + kPubWords) * 8 <= (int)kPinnedBlockBytes && kPubTaggedAt * 8 >= 512, "the tagged publication lies behind the three blocks");
+  for (int i = 0; i < kPubWords; ++i) h->host_pub[kPubTaggedAt + i] = 0ull;
   h->pub_count = 0;
   {
     void* dev_view = nullptr;
@@ -1592,7 +1600,7 @@ static int persistent_launch(cc_intrinsics* h, SolveRun* r) {
 
 static int persistent_wait(cc_intrinsics* h, SolveRun* r) {
   CC_HIP(hipSetDevice(h->device));
-  if (int rc = wait_chunk(h, &r->st)) return rc;
+  if (int rc = wait_solve(h, &r->st)) return rc;
   if (r->st.done && r->st.term == CC_FAILURE_EXCHANGE) {
     CC_HIP(hipMemsetAsync(h->pq.fail, 0, sizeof(unsigned), h->stream));
     (void)hipStreamSynchronize(h->stream);
@@ -1616,6 +1624,14 @@ static int persistent_wait(cc_intrinsics* h, SolveRun* r) {
 
 // The whole solve as one launch of the persistent kernel. Starts from buffer 0 (solve_begin moved a continued solve's
 // accepted point there) or, after set_state / reset, from the initial-state arrays.
+// The publication of a persistent solve orders nothing behind it: the kernel stores the device's control block, the intrinsics
+// and the last log record AFTER it, and what reads them on the stream (read_ctl, get_state, the next launch) is ordered by the
+// kernel's end. finish_summary copies the log beside the stream, so a caller that asked for the log waits for that end first.
+static int persistent_log_settled(cc_intrinsics* h, const cc_summary* summary) {
+  if (summary && summary->log && summary->log_capacity > 0) CC_HIP(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 static int solve_persistent(cc_intrinsics* h, SolveRun* r) {
   // (one persistent launch per device and process at a time: persist_mutex, cc_common.hpp; the exchanging forms -- several
   // ranks that must run together -- go through cc_intrinsics_optimize_multi's own loop or one process per rank)
@@ -1644,7 +1660,12 @@ int cc_intrinsics_solve(cc_intrinsics* h, const cc_options* opt, cc_summary* sum
     const bool was_restart = h->reset_pending;
     PersistProbe probe(h->device, 0, alone);
     const int rc = solve_persistent(h, &r);
-    if (rc == CC_OK) { probe.completed(); h->ran_form = h->pq.teams; return finish_summary(h, &r, summary); }
+    if (rc == CC_OK) {
+      probe.completed();
+      h->ran_form = h->pq.teams;
+      if (int rc2 = persistent_log_settled(h, summary)) return rc2;
+      return finish_summary(h, &r, summary);
+    }
     probe.gave_up();
     if (rc != CC_ERR_COMM || h->exchange) return rc;
     // A wait inside the kernel gave up after 1.3 s: its workgroups were not all resident (another process on the device,
@@ -1733,6 +1754,7 @@ int cc_intrinsics_optimize_multi(const cc_options* opt, int32_t n_devices, const
   if (all_persist) {
     for (int r = 0; r < n && !rc; ++r) rc = persistent_launch(hs[(size_t)r], &runs[(size_t)r]);
     for (int r = 0; r < n && !rc; ++r) rc = persistent_wait(hs[(size_t)r], &runs[(size_t)r]);
+    if (!rc) rc = persistent_log_settled(hs[0], summary);
   }
   for (int chunk = 0; !rc && !all_persist; ++chunk) {
     for (int r = 0; r < n && !rc; ++r) rc = solve_launch(hs[(size_t)r], &runs[(size_t)r], chunk);
@@ -1754,7 +1776,7 @@ int cc_intrinsics_optimize_multi(const cc_options* opt, int32_t n_devices, const
   return rc;
 }
 
-// Scripts only (not in the public header): copy of a device vector. name: "vec_solve" (timing marks of timing-only builds).
+// Scripts and tests only (not in the public header): copy of a device vector. name: "vec_solve" (timing marks of timing-only builds), "stats", "ctl".
 int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, int64_t n) {
   using namespace cc;
   if (!h || !name || !out || n < 0) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_debug_fetch: bad arguments");
@@ -1763,6 +1785,7 @@ int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, i
   int64_t cap = 0;
   if (k == "vec_solve") { src = h->d.vec_solve; cap = kVecSolve; }
   else if (k == "stats") { src = h->d.stats; cap = h->F * h->d.T * kStatsCols; }   // (timing builds of the persistent kernel: per-workgroup marks)
+  else if (k == "ctl") { src = reinterpret_cast<const double*>(h->d.ctl_next); cap = sizeof(LmCtl) / 8; }   // (the device's control block, raw words: tests/test_gpu_intr_publish.py)
   if (!src || n > cap) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_debug_fetch: unknown buffer or too long");
   CC_HIP(hipSetDevice(h->device));
   CC_HIP(hipStreamSynchronize(h->stream));

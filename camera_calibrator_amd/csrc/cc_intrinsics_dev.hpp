@@ -42,7 +42,7 @@ struct IntrDev {
   LmCtl* ctl_next;    // written by the solve step (RCCL route: also by block 0 of decide_elim); read by the host
   unsigned* arrive;   // [1] blocks of decide_elim that have stored their partial row (last-block-done)
   unsigned long long* pub_seq;   // [1] device: chunks published so far
-  unsigned long long* host_pub;  // pinned host memory: [0] sequence word, [2..19] copy of the control block
+  unsigned long long* host_pub;  // pinned host memory: [0] sequence word, [2..19] copy of the control block; [kPubTaggedAt ..): the persistent kernel's tagged copy (cc_persist_publish.hpp)
   LmOpts* opts;
   cc_iteration* log;
   int32_t log_cap;

@@ -27,6 +27,7 @@
 // everybody leaves, and a handle alone on its device runs the solve again with two kernels per iteration.
 #include "cc_intrinsics_persist.hpp"
 #include "cc_persist_dev.hpp"
+#include "cc_persist_publish.hpp"
 #include "cc_persist_sum.hpp"
 
 namespace cc {
@@ -271,12 +272,15 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
   LmOpts* s_opts = reinterpret_cast<LmOpts*>(lds + 1252);      // 12 doubles
   cc_iteration* s_log = reinterpret_cast<cc_iteration*>(lds + 1264);
   int* s_int = reinterpret_cast<int*>(lds + 1296);             // [0] gather ok, [1] a record was logged this round
+  u64* s_seq = reinterpret_cast<u64*>(lds + 1300);             // the sequence number this solve is published under
   const int tid = threadIdx.x, wave = tid >> 6;
   static_assert(sizeof(cc_iteration) <= 32 * 8, "log record scratch");
   // initial state: a fresh control block (every launch is a whole solve), options, intrinsics of the starting point
   if (tid < (int)(sizeof(LmCtl) / 8)) reinterpret_cast<double*>(s_ctl)[tid] = 0.0;
   if (tid >= 32 && tid < 32 + (int)(sizeof(LmOpts) / 8)) reinterpret_cast<u64*>(s_opts)[tid - 32] = reinterpret_cast<const u64*>(P.opts)[tid - 32];
   if (tid >= 64 && tid < 64 + 32) s_intr[tid - 64] = 0.0;
+  // (the count of publications is the same for the whole launch: read here, next to the options, not in front of the publication)
+  if (tid == 48 && P.host_pub) *s_seq = *P.pub_seq + 1ull;
   __syncthreads();
   if (tid < 9) s_intr[tid] = (Q.restart ? P.init_intr : P.intr)[tid];
   if (tid == 0) s_int[1] = 0;
@@ -361,11 +365,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
     const bool hit = s_int[2] != 0;
     if (s_ctl->done || !hit) {
       if (tid < 22) ag_st(Q.xbox + tid, granule(e2, s_bc[tid >> 1], tid & 1));
-      if (s_ctl->done) {
-        // a decision that ends the solve (tolerance, iteration limit) still owes its log record
-        if (tid == 0 && s_int[1] && s_ctl->log_len <= P.log_cap) P.log[s_ctl->log_len - 1] = *s_log;
-        break;
-      }
+      if (s_ctl->done) break;   // (a decision that ends the solve -- tolerance, iteration limit -- still owes its log record: behind the publication)
     }
     // ---- elimination rows (of the assumption, or of the second elimination after a miss) -> gradient tests, reduced solve
     const unsigned erow = hit ? e2 : e3;
@@ -469,24 +469,51 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       if (e && e->accepted) e->gradient_max_norm = gmax;
       if (!s_int[0]) { __hip_atomic_store(Q.fail, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_ctl->done = 1; s_ctl->term = CC_FAILURE_EXCHANGE; }
       else if (lm_finalize(*s_ctl, o, gmax)) { s_ctl->step_valid = ok ? 1 : 0; s_ctl->cand_pending = 1; }
-      if (e && s_ctl->log_len <= P.log_cap) P.log[s_ctl->log_len - 1] = *e;
+      if (e && s_ctl->log_len <= P.log_cap && !s_ctl->done) P.log[s_ctl->log_len - 1] = *e;   // (the record of the round that ends the solve: behind the publication)
     }
     __syncthreads();
     if (s_ctl->done) break;
   }
-  // ---- the solve is over: control block, intrinsics, publication
-  __syncthreads();
+  // ---- the solve is over: publication, then control block, intrinsics and the last log record.
+  // Everything the end needs was written by wave 0's own lanes -- the control block and the log record by thread 0, the intrinsics in
+  // the reduced solve, the sequence number in the prologue -- and a wave's LDS operations execute in order: the other waves leave,
+  // no workgroup barrier stands between the decision and the words the host is spinning on. Indices from a fresh copy of the thread id.
+  if (wave != 0) return;
+  int lane = threadIdx.x;
+  asm volatile("" : "+v"(lane));
+  wave_lds_fence();
   // (after a wait that gave up nothing is written back: buffer 0 still holds the point the solve started from, so the host
-  // can run it again in the other form)
-  if (tid < 32 && ag_ld32(Q.fail) == 0u) P.intr[tid] = s_intr[tid];
-  if (tid == 0) {
-    LmCtl c = *s_ctl;
-    if (ag_ld32(Q.fail) != 0u) { c.done = 1; c.term = CC_FAILURE_EXCHANGE; }
-    if (!c.done) { c.done = 1; c.term = CC_NO_CONVERGENCE; }
-    *P.ctl = c;
-    *P.ctl_next = c;
-    publish_to_host(P, c);
+  // can run it again in the other form. ONE read of the failure word; the LDS reads below run under its round trip.)
+  const unsigned failed = ag_ld32(Q.fail);
+  constexpr int kLogWords = (int)(sizeof(cc_iteration) / 8);
+  static_assert(sizeof(LmCtl) == kPubDoubles * 8 && sizeof(cc_iteration) % 8 == 0 && kLogWords <= 64 && kPubWords <= 64, "one word per lane");
+  static_assert(offsetof(LmCtl, done) == 0 && offsetof(LmCtl, term) == 4, "lanes 0 and 1 hold done and term");
+  unsigned half = reinterpret_cast<const unsigned*>(s_ctl)[lane < kPubWords ? lane : 0];   // half (lane & 1) of word lane / 2
+  const int done = s_ctl->done, log_len = s_ctl->log_len;
+  const bool owes_record = s_int[1] && log_len <= P.log_cap;
+  const double intr_l = s_intr[lane & 31];
+  const u64 log_l = reinterpret_cast<const u64*>(s_log)[lane < kLogWords ? lane : 0];
+  if (failed != 0u) half = lane == 0 ? 1u : lane == 1 ? (unsigned)CC_FAILURE_EXCHANGE : half;
+  else if (!done) half = lane == 0 ? 1u : lane == 1 ? (unsigned)CC_NO_CONVERGENCE : half;
+  if (P.host_pub) {
+    // Tagged words (cc_persist_publish.hpp), 36 lanes, one instruction, relaxed: each word validates itself, so no release -- no
+    // write-back of the L2 the workers are storing their poses through -- and no wait stands in front of them. The plain sequence
+    // word goes out too, unordered: the host reads it only to resynchronise its count once the stream is idle (wait_published_tagged).
+    const u64 seq = *s_seq;
+    if (lane < kPubWords) __hip_atomic_store(P.host_pub + kPubTaggedAt + lane, publish_word(publish_tag(seq), half), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (lane == 0) {
+      __hip_atomic_store(P.host_pub, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      *P.pub_seq = seq;
+    }
   }
+  // What follows is read by stream-ordered work only (read_ctl, get_state, the next launch; the host waits for the kernel's end
+  // before it copies a log): one word per lane, behind the publication.
+  if (lane < kPubWords) {
+    reinterpret_cast<unsigned*>(P.ctl)[lane] = half;
+    reinterpret_cast<unsigned*>(P.ctl_next)[lane] = half;
+  }
+  if (lane < 32 && failed == 0u) P.intr[lane] = intr_l;
+  if (owes_record && lane < kLogWords) reinterpret_cast<u64*>(P.log + (log_len - 1))[lane] = log_l;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "cc_common.hpp"
+#include "cc_persist_publish.hpp"
 
 namespace cc {
 
@@ -121,6 +122,43 @@ static int wait_published(SolveHost* h, hipStream_t stream2, LmCtl* c, bool* wai
   }
   std::memcpy(c, word + 2, sizeof(LmCtl));
   if (wait_failed) *wait_failed = h->host_pub[2 + sizeof(LmCtl) / 8] != 0ull;
+  return 0;
+}
+
+// The same wait for a whole solve of the persistent intrinsics kernel, which publishes its control block as tagged words
+// (cc_persist_publish.hpp) at host_pub + kPubTaggedAt: spins until a copy of the kPubWords words, taken word by word, carries the
+// tag of the count this wait expects in every word, and reassembles the block from that copy. No word of the block is ordered
+// against another, and none against the plain sequence word host_pub[0], which the kernel still stores: it is what the fallback
+// -- the one of wait_published, unchanged -- resynchronises the count from once the stream has gone idle.
+template <class ReadCtl>
+static int wait_published_tagged(SolveHost* h, LmCtl* c, const char* who, ReadCtl read_ctl) {
+  static_assert(sizeof(LmCtl) == kPubDoubles * 8, "the tagged publication carries the whole control block");
+  const unsigned long long* word = const_cast<const unsigned long long*>(h->host_pub);
+  const unsigned long long* tagged = word + kPubTaggedAt;
+  const uint32_t want = publish_tag(++h->pub_count);
+  unsigned long long copy[kPubWords];
+  auto arrived = [&] {
+    for (int i = kPubWords - 1; i >= 0; --i) {
+      copy[i] = __atomic_load_n(tagged + i, __ATOMIC_RELAXED);
+      if ((uint32_t)(copy[i] >> 32) != want) return false;
+    }
+    return publish_ready(copy, want);
+  };
+  for (unsigned spins = 0;; ++spins) {
+    if (arrived()) break;
+    if ((spins & 0xfffu) == 0xfffu) {
+      const hipError_t q = hipStreamQuery(h->stream);
+      if (q == hipSuccess) {
+        if (arrived()) break;
+        h->pub_count = __atomic_load_n(word, __ATOMIC_ACQUIRE);
+        return read_ctl();
+      }
+      if (q != hipErrorNotReady) return fail(CC_ERR_HIP, "stream failed while waiting for %s: %s", who, hipGetErrorString(q));
+    }
+  }
+  unsigned long long block[kPubDoubles];
+  publish_unpack(copy, block);
+  std::memcpy(c, block, sizeof(LmCtl));
   return 0;
 }
 
