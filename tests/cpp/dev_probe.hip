@@ -1,4 +1,4 @@
-// dev_probe.hip -- test-only probe of the shared device primitives (tests/test_gpu_dev_primitives.py). One thin kernel per
+// dev_probe.hip -- test-only probe of the shared device primitives (tests/test_gpu_dev_primitives.py) and of the stages of Zhang's initialisation (tests/test_gpu_zhang_stages.py). One thin kernel per
 // primitive around the inlined helper, one extern "C" entry per kernel: copy in, one launch, synchronise, copy out. Built by
 // `make probe` in camera_calibrator_amd/csrc with the product's flags (contraction and fast-math settings decide the
 // arithmetic of inlined code); never linked into libcc_hip.so. Nothing here waits or spins: the polling helpers of
@@ -10,6 +10,7 @@
 #include "cc_device.hpp"
 #include "cc_persist_dev.hpp"
 #include "cc_rig_dev.hpp"
+#include "cc_zhang_dev.hpp"
 
 namespace {
 
@@ -221,6 +222,39 @@ __global__ __launch_bounds__(256) void k_chol_block4(int S, const double* M /*[n
   ok[sys * 256 + tid] = okb ? 1 : 0;
 }
 
+// ---- Zhang initialisation (cc_zhang_dev.hpp): the four kernels are launched as they are; these two wrap the helpers they
+// inline. One thread per matrix, as k_zhang_eig9 has it.
+template <int N>
+__global__ __launch_bounds__(64) void k_smallest_eigvec(int64_t count, const double* A /*[count][N][N]*/, double* x /*[count][N]*/) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= count) return;
+  double a[N][N], v[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) a[i][j] = A[f * N * N + i * N + j];
+  smallest_eigvec<N>(a, v);
+#pragma unroll
+  for (int i = 0; i < N; ++i) x[f * N + i] = v[i];
+}
+__global__ __launch_bounds__(64) void k_jacobi_eigen3(int64_t count, const double* S /*[count][3][3]*/, double* lam /*[count][3]*/,
+                                                      double* V /*[count][3][3]*/) {
+  const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= count) return;
+  double s[3][3], v[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s[i][j] = S[f * 9 + i * 3 + j];
+  jacobi_eigen<3>(s, v, 10);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    lam[f * 3 + i] = s[i][i];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) V[f * 9 + i * 3 + j] = v[i][j];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -333,6 +367,61 @@ int probe_chol_block4(int S, int nsys, const double* M, double* x, int* ok) {
   hipLaunchKernelGGL(k_chol_block4, dim3(nsys), dim3(256), 0, 0, S, d_M, d_x, d_ok);
   PROBE_TRY(finish(x, d_x, (size_t)nsys * 64));
   return (int)hipMemcpy(ok, d_ok, (size_t)nsys * 256 * sizeof(int), hipMemcpyDeviceToHost);
+}
+
+// k_zhang_gram itself, with its own block size and LDS size: off[F + 1], uv[off[F]][2], xyz[off[F]][3] -> gram[F][256]
+int probe_zhang_gram(long long F, const long long* off, const float* uv, const float* xyz, double* gram) {
+  if (F < 1 || F > 4096 || !off || off[0] != 0) return -1;
+  for (long long f = 0; f < F; ++f)
+    if (off[f + 1] <= off[f]) return -1;   // (every frame has a point: the padding lanes re-read point off[f])
+  const size_t N = (size_t)off[F];
+  if (N > ((size_t)1 << 24)) return -1;
+  Bufs B; int64_t* d_off; float *d_uv, *d_xyz; double* d_gram;
+  static_assert(sizeof(long long) == sizeof(int64_t), "offsets are passed as they are");
+  PROBE_TRY(B.in(&d_off, (const int64_t*)off, (size_t)F + 1)); PROBE_TRY(B.in(&d_uv, uv, N * 2)); PROBE_TRY(B.in(&d_xyz, xyz, N * 3));
+  PROBE_TRY(B.out(&d_gram, (size_t)F * 256));
+  hipLaunchKernelGGL(k_zhang_gram, dim3((unsigned)F), dim3(kZhangThreads), kZhangLdsBytes, 0, (int64_t)F, d_off, d_uv, d_xyz, d_gram);
+  return (int)finish(gram, d_gram, (size_t)F * 256);
+}
+int probe_smallest_eigvec(int N, long long count, const double* A, double* x) {
+  if ((N != 6 && N != 9) || count < 1 || count > (1 << 20)) return -1;
+  Bufs B; double *d_A, *d_x;
+  PROBE_TRY(B.in(&d_A, A, (size_t)count * N * N)); PROBE_TRY(B.out(&d_x, (size_t)count * N));
+  const dim3 grid((unsigned)((count + 63) / 64));
+  if (N == 6) hipLaunchKernelGGL(k_smallest_eigvec<6>, grid, dim3(64), 0, 0, (int64_t)count, d_A, d_x);
+  else hipLaunchKernelGGL(k_smallest_eigvec<9>, grid, dim3(64), 0, 0, (int64_t)count, d_A, d_x);
+  return (int)finish(x, d_x, (size_t)count * N);
+}
+int probe_zhang_eig9(long long F, const double* gram /*[F][256]*/, float* H /*[F][9]*/) {
+  if (F < 1 || F > (1 << 20)) return -1;
+  Bufs B; double* d_gram; float* d_H;
+  PROBE_TRY(B.in(&d_gram, gram, (size_t)F * 256)); PROBE_TRY(B.out(&d_H, (size_t)F * 9));
+  hipLaunchKernelGGL(k_zhang_eig9, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, 0, (int64_t)F, d_gram, d_H);
+  return (int)finish(H, d_H, (size_t)F * 9);
+}
+int probe_zhang_k(long long F, const float* Hs /*[F][9]*/, float* K9) {
+  if (F < 1 || F > (1 << 20)) return -1;
+  Bufs B; float *d_H, *d_K;
+  PROBE_TRY(B.in(&d_H, Hs, (size_t)F * 9)); PROBE_TRY(B.out(&d_K, 9));
+  hipLaunchKernelGGL(k_zhang_k, dim3(1), dim3(256), 0, 0, (int64_t)F, d_H, d_K);
+  return (int)finish(K9, d_K, 9);
+}
+int probe_zhang_poses(long long F, const float* Hs /*[F][9]*/, const float* K9, float* q /*[F][4]*/, float* t /*[F][3]*/) {
+  if (F < 1 || F > (1 << 20)) return -1;
+  Bufs B; float *d_H, *d_K, *d_q, *d_t;
+  PROBE_TRY(B.in(&d_H, Hs, (size_t)F * 9)); PROBE_TRY(B.in(&d_K, K9, 9));
+  PROBE_TRY(B.out(&d_q, (size_t)F * 4)); PROBE_TRY(B.out(&d_t, (size_t)F * 3));
+  hipLaunchKernelGGL(k_zhang_poses, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, 0, (int64_t)F, d_H, d_K, d_q, d_t);
+  PROBE_TRY(finish(q, d_q, (size_t)F * 4));
+  return (int)hipMemcpy(t, d_t, (size_t)F * 3 * sizeof(float), hipMemcpyDeviceToHost);
+}
+int probe_jacobi_eigen3(long long count, const double* S /*[count][3][3]*/, double* eigenvalues /*[count][3]*/, double* V /*[count][3][3]*/) {
+  if (count < 1 || count > (1 << 20)) return -1;
+  Bufs B; double *d_S, *d_l, *d_V;
+  PROBE_TRY(B.in(&d_S, S, (size_t)count * 9)); PROBE_TRY(B.out(&d_l, (size_t)count * 3)); PROBE_TRY(B.out(&d_V, (size_t)count * 9));
+  hipLaunchKernelGGL(k_jacobi_eigen3, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, (int64_t)count, d_S, d_l, d_V);
+  PROBE_TRY(finish(eigenvalues, d_l, (size_t)count * 3));
+  return (int)hipMemcpy(V, d_V, (size_t)count * 9 * sizeof(double), hipMemcpyDeviceToHost);
 }
 
 }  // extern "C"

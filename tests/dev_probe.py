@@ -14,6 +14,9 @@ _ip = ctypes.POINTER(ctypes.c_int)
 _up = ctypes.POINTER(ctypes.c_uint)
 _qp = ctypes.POINTER(ctypes.c_ulonglong)
 _i = ctypes.c_int
+_ll = ctypes.c_longlong
+_lp = ctypes.POINTER(ctypes.c_longlong)
+_fp = ctypes.POINTER(ctypes.c_float)
 
 
 def lib():
@@ -38,6 +41,12 @@ def lib():
             "probe_spec_radius": [_i, _dp, _dp, _dp],
             "probe_chol_rows": [_i, _i, _dp, _dp, _dp, _ip],
             "probe_chol_block4": [_i, _i, _dp, _dp, _ip],
+            "probe_zhang_gram": [_ll, _lp, _fp, _fp, _dp],
+            "probe_smallest_eigvec": [_i, _ll, _dp, _dp],
+            "probe_zhang_eig9": [_ll, _dp, _fp],
+            "probe_zhang_k": [_ll, _fp, _fp],
+            "probe_zhang_poses": [_ll, _fp, _fp, _fp, _fp],
+            "probe_jacobi_eigen3": [_ll, _dp, _dp, _dp],
         }.items():
             f = getattr(L, name)
             f.argtypes = args
@@ -198,3 +207,71 @@ def chol_block4(M):
     x, ok = np.empty((nsys, 64)), np.empty((nsys, 256), dtype=np.int32)
     _ok(lib().probe_chol_block4(S, nsys, _p(M), _p(x), _p(ok, _ip)), "chol_block4")
     return x[:, :S].copy(), ok
+
+
+# ---- Zhang initialisation (cc_zhang_dev.hpp)
+def _f(a, shape=None):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if shape is not None:
+        assert a.shape == shape, (a.shape, shape)
+    return a
+
+
+def zhang_gram(off, uv, xyz):
+    """k_zhang_gram: off[F + 1], uv[N][2], xyz[N][3] (float32) -> gram[F][16][16]."""
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    F, N = len(off) - 1, int(off[-1])
+    uv, xyz = _f(uv, (N, 2)), _f(xyz, (N, 3))
+    out = np.empty((F, 16, 16))
+    _ok(lib().probe_zhang_gram(F, _p(off, _lp), _p(uv, _fp), _p(xyz, _fp), _p(out)), "k_zhang_gram")
+    return out
+
+
+def smallest_eigvec(A):
+    """smallest_eigvec<N>, N = 6 or 9: A[count][N][N] -> x[count][N] (doubles, before any rounding to float)."""
+    A = _d(A)
+    count, N = A.shape[0], A.shape[1]
+    assert A.shape == (count, N, N)
+    out = np.empty((count, N))
+    _ok(lib().probe_smallest_eigvec(N, count, _p(A), _p(out)), "smallest_eigvec")
+    return out
+
+
+def zhang_eig9(gram):
+    """k_zhang_eig9: gram[F][16][16] -> H[F][3][3] float32."""
+    gram = _d(gram)
+    F = gram.shape[0]
+    assert gram.shape == (F, 16, 16)
+    out = np.empty((F, 3, 3), dtype=np.float32)
+    _ok(lib().probe_zhang_eig9(F, _p(gram), _p(out, _fp)), "k_zhang_eig9")
+    return out
+
+
+def zhang_k(Hs):
+    """k_zhang_k: Hs[F][3][3] float32 -> K[3][3] float32."""
+    Hs = _f(Hs)
+    F = Hs.shape[0]
+    assert Hs.shape == (F, 3, 3)
+    out = np.empty((3, 3), dtype=np.float32)
+    _ok(lib().probe_zhang_k(F, _p(Hs, _fp), _p(out, _fp)), "k_zhang_k")
+    return out
+
+
+def zhang_poses(Hs, K):
+    """k_zhang_poses: Hs[F][3][3], K[3][3] float32 -> q[F][4] (w x y z), t[F][3] float32."""
+    Hs, K = _f(Hs), _f(K, (3, 3))
+    F = Hs.shape[0]
+    assert Hs.shape == (F, 3, 3)
+    q, t = np.empty((F, 4), dtype=np.float32), np.empty((F, 3), dtype=np.float32)
+    _ok(lib().probe_zhang_poses(F, _p(Hs, _fp), _p(K, _fp), _p(q, _fp), _p(t, _fp)), "k_zhang_poses")
+    return q, t
+
+
+def jacobi_eigen3(S):
+    """jacobi_eigen<3>(S, V, 10): S[count][3][3] -> (eigenvalues[count][3], V[count][3][3], eigenvectors in columns)."""
+    S = _d(S)
+    count = S.shape[0]
+    assert S.shape == (count, 3, 3)
+    lam, V = np.empty((count, 3)), np.empty((count, 3, 3))
+    _ok(lib().probe_jacobi_eigen3(count, _p(S), _p(lam), _p(V)), "jacobi_eigen<3>")
+    return lam, V
