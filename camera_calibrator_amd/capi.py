@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = [
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
     "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
+    "cc_rig_start_options_init", "cc_rig_estimate_start", "cc_rig_start_views", "cc_rig_estimate",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
     "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
     "cc_intrinsics_set_huber", "cc_intrinsics_obs_cost", "cc_intrinsics_optimize_views_huber", "cc_intrinsics_estimate_views_huber",
@@ -714,6 +715,17 @@ def rig_optimize_columns(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, worl
     return cam_q, cam_t, frame_q, frame_t, cost, _summary_dict(s, log)
 
 
+class RigStartOptions(C.Structure):
+    _fields_ = [("refine_iterations", C.c_int32)]
+
+
+class RigStartReport(C.Structure):
+    _fields_ = [("views_valid", C.c_int64), ("views_planar", C.c_int64), ("views_general", C.c_int64), ("views_invalid", C.c_int64),
+                ("frames_placed", C.c_int64), ("frames_unplaced", C.c_int64), ("cameras_placed", C.c_int32),
+                ("cameras_unplaced", C.c_int32), ("root_camera", C.c_int32), ("root_at_identity", C.c_int32),
+                ("parent", C.POINTER(C.c_int32))]
+
+
 class RigProblem:
     """Handle on a rig pose problem resident in HBM (cc_rig_*)."""
 
@@ -842,6 +854,39 @@ class RigProblem:
         _check(lib().cc_rig_inner_status(self._h, C.byref(p), C.byref(u), C.byref(e), C.byref(r)))
         return dict(passes=p.value, useful_passes=u.value, enabled_at_end=e.value, cost_removed=r.value)
 
+    def estimate_start(self, cam_q=None, cam_t=None, frame_q=None, frame_t=None, refine_iterations=10):
+        """Start poses from the handle's own observations (cc_rig_estimate_start): they become the handle's state as set_state
+        would have set it. The four arrays are the caller's poses (None: the identity), kept for frozen cameras, cameras without
+        a path to the root and frames without a valid view. Returns the report as a dict (parent: one entry per camera)."""
+        opt = RigStartOptions(refine_iterations=int(refine_iterations))
+        rep = RigStartReport()
+        parent = np.full(self.n_cams, -1, dtype=np.int32)
+        rep.parent = _p(parent, C.c_int32)
+        arrs = []
+        for a, n in ((cam_q, 4 * self.n_cams), (cam_t, 3 * self.n_cams), (frame_q, 4 * self.n_frames), (frame_t, 3 * self.n_frames)):
+            if a is not None:
+                a = _f64(a)
+                assert a.size == n
+            arrs.append(a)
+        _check(lib().cc_rig_estimate_start(self._h, C.byref(opt), *[_p(a, C.c_double) if a is not None else None for a in arrs],
+                                           C.byref(rep)))
+        out = {k: int(getattr(rep, k)) for k, _ in RigStartReport._fields_ if k != "parent"}
+        out["parent"] = parent
+        return out
+
+    def start_views(self):
+        """What the last estimate_start computed per view (cc_rig_start_views), in (frame, camera) order: dict of camera, frame,
+        kind (0 invalid, 1 planar, 2 general), q [n, 4], t [n, 3], rms2 [n]."""
+        n = C.c_int64(0)
+        _check(lib().cc_rig_start_views(self._h, C.byref(n), None, None, None, None, None, None))
+        n = int(n.value)
+        cam, frame, kind = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        q, t, rms2 = np.zeros((n, 4)), np.zeros((n, 3)), np.zeros(n)
+        nn = C.c_int64(0)
+        _check(lib().cc_rig_start_views(self._h, C.byref(nn), _p(cam, C.c_int32), _p(frame, C.c_int64), _p(kind, C.c_int32),
+                                        _p(q, C.c_double), _p(t, C.c_double), _p(rms2, C.c_double)))
+        return dict(camera=cam, frame=frame, kind=kind, q=q, t=t, rms2=rms2)
+
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))
         _check(lib().cc_rig_comm_init(self._h, buf, C.c_int32(rank), C.c_int32(nranks)))
@@ -885,6 +930,36 @@ def rig_optimize(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, c
                                            _p(cost, C.c_double), C.byref(s)))
         return cam_q, cam_t, frame_q, frame_t, cost, _summary_dict(s, log)
     _check(lib().cc_rig_optimize(C.byref(opt), C.c_int32(device), C.c_int64(n_cams), C.c_int64(F),
+                                 C.c_int64(world_xyz.size // 3), _p(off, C.c_int64), _p(obs_cam, C.c_uint32),
+                                 _p(obs_world, C.c_uint64), _p(obs_uv, C.c_float), _p(world_xyz, C.c_float),
+                                 _p(cam_q, C.c_double), _p(cam_t, C.c_double), _p(frozen, C.c_uint8),
+                                 _p(frame_q, C.c_double), _p(frame_t, C.c_double), C.c_double(huber_a),
+                                 _p(cost, C.c_double), C.byref(s)))
+    return cam_q, cam_t, frame_q, frame_t, cost, _summary_dict(s, log)
+
+
+def rig_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, cam_frozen, cam_q=None, cam_t=None, frame_q=None,
+                 frame_t=None, huber_a=HUBER_A, options=None, device=0, log_capacity=2048):
+    """One-shot cc_rig_estimate: start poses from the observations, then the solve. The pose arrays are the caller's poses
+    (None: the identity). Returns (cam_q, cam_t, frame_q, frame_t, obs_cost, summary)."""
+    off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+    F = len(off) - 1
+    obs_cam = np.ascontiguousarray(obs_cam, dtype=np.uint32)
+    obs_world = np.ascontiguousarray(obs_world, dtype=np.uint64)
+    obs_uv, world_xyz = _f32(obs_uv), _f32(world_xyz)
+    frozen = np.ascontiguousarray(cam_frozen, dtype=np.uint8)
+    ident = np.array([1.0, 0.0, 0.0, 0.0])
+    cam_q = np.tile(ident, (n_cams, 1)) if cam_q is None else _f64(cam_q).copy()
+    cam_t = np.zeros((n_cams, 3)) if cam_t is None else _f64(cam_t).copy()
+    frame_q = np.tile(ident, (F, 1)) if frame_q is None else _f64(frame_q).copy()
+    frame_t = np.zeros((F, 3)) if frame_t is None else _f64(frame_t).copy()
+    cost = np.zeros(len(obs_cam))
+    opt = options if options is not None else default_options(max_iterations=1000)
+    log = (Iteration * max(1, log_capacity))()
+    s = Summary()
+    s.log = C.cast(log, C.POINTER(Iteration))
+    s.log_capacity = log_capacity
+    _check(lib().cc_rig_estimate(C.byref(opt), C.c_int32(device), C.c_int64(n_cams), C.c_int64(F),
                                  C.c_int64(world_xyz.size // 3), _p(off, C.c_int64), _p(obs_cam, C.c_uint32),
                                  _p(obs_world, C.c_uint64), _p(obs_uv, C.c_float), _p(world_xyz, C.c_float),
                                  _p(cam_q, C.c_double), _p(cam_t, C.c_double), _p(frozen, C.c_uint8),

@@ -176,6 +176,17 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("AddWorldPoint", &ExtrinsicsCalibrator::AddWorldPoint, py::arg("frame_id"), py::arg("world_point"))
       .def("AddObservation", &ExtrinsicsCalibrator::AddObservation, py::arg("camera_id"), py::arg("world_point_id"), py::arg("image_point"))
       .def("Optimize", &ExtrinsicsCalibrator::Optimize)
+      .def("EstimateInitialPoses", &ExtrinsicsCalibrator::EstimateInitialPoses)
+      .def("Estimate", &ExtrinsicsCalibrator::Estimate)
+      .def("LastStartReport", [](const ExtrinsicsCalibrator& self) {
+        const ExtrinsicsCalibrator::StartReport& r = self.LastStartReport();
+        py::dict d;
+        d["views_valid"] = r.views_valid; d["views_planar"] = r.views_planar; d["views_general"] = r.views_general;
+        d["views_invalid"] = r.views_invalid; d["frames_placed"] = r.frames_placed; d["frames_unplaced"] = r.frames_unplaced;
+        d["cameras_placed"] = r.cameras_placed; d["cameras_unplaced"] = r.cameras_unplaced; d["root_camera"] = r.root_camera;
+        d["root_at_identity"] = r.root_at_identity; d["parent"] = r.parent;
+        return d;
+      })
       .def("Serialize", &ExtrinsicsCalibrator::Serialize, py::arg("fname"))
       .def("Parse", &ExtrinsicsCalibrator::Parse, py::arg("fname"))
       .def("RemoveObservationFrame", &ExtrinsicsCalibrator::RemoveObservationFrame, py::arg("observation_frame_id"))

@@ -274,6 +274,72 @@ void ExtrinsicsCalibrator::Optimize() {
   last_timing_ms_[3] = std::chrono::duration<double, std::milli>(t_end - t_call).count();
 }
 
+// ---- start poses from the observations -------------------------------------------------------------------
+// (a call per recording, not per iteration: plain flat copies of the observations, the handle API)
+void ExtrinsicsCalibrator::EstimateInitialPoses() {
+  const size_t C = cameras_.size(), F = frames_.size(), Pn = point_refs_.size();
+  start_report_ = StartReport{};
+  start_report_.parent.assign(C, -1);
+  if (devices_.size() > 1) {
+    last_status_ = CC_ERR_STATE;
+    return;
+  }
+  std::vector<int64_t> offsets(F + 1, 0);
+  for (size_t f = 0; f < F; ++f) offsets[f + 1] = offsets[f] + (int64_t)frames_[f].NumObservations();
+  const size_t N = (size_t)offsets[F];
+  last_status_ = 0;
+  if (N == 0 || C == 0 || F == 0) {
+    last_status_ = CC_ERR_STATE;   // (no camera is observed)
+    return;
+  }
+  std::vector<uint32_t> obs_cam(N);
+  std::vector<uint64_t> obs_world(N);
+  std::vector<float> obs_uv(2 * N), world(3 * Pn);
+  for (size_t f = 0; f < F; ++f) {
+    const Frame& fr = frames_[f];
+    const size_t k0 = (size_t)offsets[f], n = fr.NumObservations();
+    if (n == 0) continue;
+    std::memcpy(obs_cam.data() + k0, fr.obs_camera.data(), n * sizeof(uint32_t));
+    std::memcpy(obs_world.data() + k0, fr.obs_point_global.data(), n * sizeof(uint64_t));
+    std::memcpy(obs_uv.data() + 2 * k0, fr.obs_normalised.data(), n * 2 * sizeof(float));
+  }
+  for (size_t i = 0; i < Pn; ++i) {
+    const Point3D& p = frames_[point_refs_[i].frame].points[point_refs_[i].point_in_frame];
+    world[3 * i] = p.x(); world[3 * i + 1] = p.y(); world[3 * i + 2] = p.z();
+  }
+  std::vector<uint8_t> frozen(C, 0);
+  for (size_t id : frozen_) if (id < C) frozen[id] = 1;
+  std::vector<double> cam_q(4 * C), cam_t(3 * C), frame_q(4 * F), frame_t(3 * F);
+  for (size_t i = 0; i < C; ++i) AffineToQuaternionTranslation(cameras_[i], &cam_q[4 * i], &cam_t[3 * i]);
+  for (size_t i = 0; i < F; ++i) AffineToQuaternionTranslation(frames_[i].pose, &frame_q[4 * i], &frame_t[3 * i]);
+  cc_rig* h = nullptr;
+  std::vector<int32_t> parent(C, -1);
+  cc_rig_start_report rep{};
+  rep.parent = parent.data();
+  last_status_ = cc_rig_create(device_, (int64_t)C, (int64_t)F, (int64_t)Pn, offsets.data(), obs_cam.data(), obs_world.data(), obs_uv.data(),
+                               world.data(), frozen.data(), 3.0f / 500.0f, &h);
+  if (last_status_ == 0) last_status_ = cc_rig_estimate_start(h, nullptr, cam_q.data(), cam_t.data(), frame_q.data(), frame_t.data(), &rep);
+  if (last_status_ == 0) last_status_ = cc_rig_get_state(h, cam_q.data(), cam_t.data(), frame_q.data(), frame_t.data(), nullptr);
+  if (h) cc_rig_destroy(h);
+  if (last_status_ == CC_ERR_NO_DEVICE || last_status_ == CC_ERR_HIP || last_status_ == CC_ERR_BAD_ARGUMENT)
+    throw std::runtime_error(std::string("ExtrinsicsCalibrator::EstimateInitialPoses: ") + cc_last_error());  // no silent CPU path
+  if (last_status_ != 0) return;
+  start_report_.views_valid = rep.views_valid; start_report_.views_planar = rep.views_planar;
+  start_report_.views_general = rep.views_general; start_report_.views_invalid = rep.views_invalid;
+  start_report_.frames_placed = rep.frames_placed; start_report_.frames_unplaced = rep.frames_unplaced;
+  start_report_.cameras_placed = rep.cameras_placed; start_report_.cameras_unplaced = rep.cameras_unplaced;
+  start_report_.root_camera = rep.root_camera; start_report_.root_at_identity = rep.root_at_identity != 0;
+  start_report_.parent.assign(parent.begin(), parent.end());
+  // poses back through float, as Optimize stores them
+  for (size_t i = 0; i < C; ++i) cameras_[i] = QuaternionTranslationToAffine(&cam_q[4 * i], &cam_t[3 * i]);
+  for (size_t i = 0; i < F; ++i) frames_[i].pose = QuaternionTranslationToAffine(&frame_q[4 * i], &frame_t[3 * i]);
+}
+
+void ExtrinsicsCalibrator::Estimate() {
+  EstimateInitialPoses();
+  if (last_status_ == 0) Optimize();
+}
+
 // ---- JSON wire format (reference: extrinsics_calibrator.cpp:268-413) -----------------------------
 
 namespace {

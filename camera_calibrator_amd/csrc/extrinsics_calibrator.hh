@@ -33,6 +33,27 @@ class ExtrinsicsCalibrator {
   /// per-observation costs; prints one progress line per iteration like the reference does.
   void Optimize();
 
+  // ---- start poses from the observations (an addition of this build; cc_rig_estimate_start in include/cc_solver.h) ----
+  /// What the last EstimateInitialPoses() did: views by kind, cameras and frames placed, the root camera, every camera's parent
+  /// in the spanning tree (-1: root, frozen or not reached).
+  struct StartReport {
+    int64_t views_valid{0}, views_planar{0}, views_general{0}, views_invalid{0};
+    int64_t frames_placed{0}, frames_unplaced{0};
+    int cameras_placed{0}, cameras_unplaced{0};
+    int root_camera{-1};
+    bool root_at_identity{false};
+    std::vector<int> parent;
+  };
+  /// Computes camera_T_rig of every camera that is not frozen and rig_T_world of every frame from the observations alone, on the
+  /// GPU, and writes them into the stored transforms: the poses given to AddCameraTRig / AddObservationFrame may all be the
+  /// identity. Frozen cameras keep their pose; so do cameras without a path of shared frames to the root and frames without a
+  /// usable view (LastStartReport() counts them). One device: with SetDevices of several, LastStatus() becomes CC_ERR_STATE and
+  /// nothing changes.
+  void EstimateInitialPoses();
+  const StartReport& LastStartReport() const { return start_report_; }
+  /// EstimateInitialPoses(), then Optimize().
+  void Estimate();
+
   void Serialize(const std::string& fname) const;
   void Parse(const std::string& fname);
 
@@ -120,6 +141,7 @@ class ExtrinsicsCalibrator {
   int last_solver_form_{0};
   std::string last_solver_note_;
   double last_final_cost_{0.0};
+  StartReport start_report_;
   // flat copies of the observations for the C ABI, kept between calls (grow-only: a caller that optimises again after adding
   // frames -- the reference's workflow -- does not fault in 200 MB of fresh vectors per call at BASELINE configs[4] size)
   // (not copied with the object; handed to the next object when this one goes: extrinsics_calibrator.cpp)

@@ -451,6 +451,45 @@ int cc_rig_get_state(cc_rig* h, double* cam_q, double* cam_t, double* frame_q, d
                      double* obs_cost);
 /* Total robustified cost at the current point (one sweep; this rank's observations only). */
 int cc_rig_eval(cc_rig* h, double* cost);
+/* EXTENSION: start poses from the handle's own observations, on the device (the reference takes its start from OpenCV solvePnP
+ * in a helper package; cc_rig_set_state needs poses). A VIEW is one camera's observations in one frame.
+ *   V  every view in closed form: planar views (>= 4 points, the board anywhere in the world) by a homography in the board's
+ *      own basis, general views (>= 6 points) by a 3 x 4 DLT, both on centred and scaled points; collinear or coincident
+ *      points, too few points or a non-finite coordinate make the view INVALID: it is skipped and counted
+ *   R  at most refine_iterations Levenberg-Marquardt steps on the view's six pose coordinates (residual x/z - u, y/z - v, no
+ *      loss function); 0: the closed form as it is
+ *   T  a spanning tree over the cameras by co-visible valid views, rooted at the observed frozen camera with the most valid
+ *      views (none frozen: the observed camera with the most valid views, placed at the identity); frozen cameras keep the
+ *      caller's pose; ties go to the lowest index
+ *   C  camera_T_rig along the tree: per (child, parent) edge the mean relative pose over the co-visible frames, weighted by
+ *      1 / (rms^2 of the child's view + rms^2 of the parent's)
+ *   F  rig_T_world of every frame: mean over its valid views of placed cameras, weighted by 1 / rms^2
+ * cam_q / cam_t / frame_q / frame_t are the caller's poses (NULL: the identity): used for frozen cameras, for cameras without a
+ * path to the root and for frames without a valid view of a placed camera. The result becomes the handle's state as
+ * cc_rig_set_state would have set it (cc_rig_reset returns to it); read it with cc_rig_get_state. opt and report may be NULL;
+ * report->parent (may be NULL) receives n_cams entries: the parent of every estimated camera, -1 for the root, frozen and
+ * unplaced cameras.
+ * cc_rig_start_views reads back stages V and R of the last call, one entry per view in (frame, camera) order: n_views first
+ * (the other outputs may be NULL; they hold n_views entries, q 4 and t 3 doubles each), kind 0 invalid / 1 planar / 2 general,
+ * rms2 = mean squared residual per observation coordinate.
+ * CC_ERR_STATE, the handle unchanged: a cc_rigk_* handle (pixel observations need the lens model first), a handle with an
+ * exchange or a communicator, a handle none of whose cameras is observed. */
+typedef struct cc_rig_start_options {
+  int32_t refine_iterations;   /* default 10 */
+} cc_rig_start_options;
+void cc_rig_start_options_init(cc_rig_start_options* o);
+typedef struct cc_rig_start_report {
+  int64_t views_valid, views_planar, views_general, views_invalid;
+  int64_t frames_placed, frames_unplaced;
+  int32_t cameras_placed, cameras_unplaced;
+  int32_t root_camera;         /* -1: no camera has a valid view */
+  int32_t root_at_identity;    /* the root is not frozen: it defines the rig frame */
+  int32_t* parent;             /* caller array of n_cams entries, or NULL */
+} cc_rig_start_report;
+int cc_rig_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t,
+                          const double* frame_q, const double* frame_t, cc_rig_start_report* report);
+int cc_rig_start_views(cc_rig* h, int64_t* n_views, int32_t* view_cam, int64_t* view_frame, int32_t* kind, double* q, double* t,
+                       double* rms2);
 /* Multi-GPU: each rank creates its handle with a contiguous shard of frames (cc_partition_frames on
  * obs_frame_offsets) and ALL cameras / world points; then attaches as for the intrinsics problem.
  * Per LM iteration: one all-reduce of the reduced (6C)x(6C) system (PC + 32 doubles) and one of
@@ -505,6 +544,13 @@ int cc_rigk_get_model(cc_rig* h, int32_t* model);
 /* One-shot: the call ExtrinsicsCalibrator::Optimize makes in place of
  * extrinsics_calibrator.cpp:92-225. opt == NULL -> cc_options_init with max_iterations = 1000. */
 int cc_rig_optimize(const cc_options* opt, int32_t device, int64_t n_cams, int64_t n_frames,
+                    int64_t n_world, const int64_t* obs_frame_offsets, const uint32_t* obs_cam,
+                    const uint64_t* obs_world, const float* obs_uv, const float* world_xyz,
+                    double* cam_q, double* cam_t, const uint8_t* cam_frozen, double* frame_q,
+                    double* frame_t, double huber_a, double* obs_cost, cc_summary* summary);
+/* EXTENSION: start, then solve, behind one upload -- cc_rig_create, cc_rig_estimate_start (default options) with the poses
+ * passed in as the caller's, cc_rig_solve, cc_rig_get_state. Same argument list as cc_rig_optimize. */
+int cc_rig_estimate(const cc_options* opt, int32_t device, int64_t n_cams, int64_t n_frames,
                     int64_t n_world, const int64_t* obs_frame_offsets, const uint32_t* obs_cam,
                     const uint64_t* obs_world, const float* obs_uv, const float* world_xyz,
                     double* cam_q, double* cam_t, const uint8_t* cam_frozen, double* frame_q,
