@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "cc_rig_create", "cc_rig_destroy", "cc_rig_set_state", "cc_rig_reset", "cc_rig_solve",
     "cc_rig_get_state", "cc_rig_solver_form", "cc_rig_solver_status", "cc_rig_eval", "cc_rig_optimize", "cc_rig_comm_init", "cc_rig_exchange_export", "cc_rig_exchange_attach", "cc_rigk_create",
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
-    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
+    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_rigk_estimate_start", "cc_rigk_start_points", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
     "cc_rig_start_options_init", "cc_rig_estimate_start", "cc_rig_start_views", "cc_rig_estimate",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
@@ -858,6 +858,15 @@ class RigProblem:
         """Start poses from the handle's own observations (cc_rig_estimate_start): they become the handle's state as set_state
         would have set it. The four arrays are the caller's poses (None: the identity), kept for frozen cameras, cameras without
         a path to the root and frames without a valid view. Returns the report as a dict (parent: one entry per camera)."""
+        return self._estimate_start(lib().cc_rig_estimate_start, cam_q, cam_t, frame_q, frame_t, refine_iterations)
+
+    def estimate_start_pixels(self, cam_q=None, cam_t=None, frame_q=None, frame_t=None, refine_iterations=10):
+        """estimate_start for a with_intrinsics handle (cc_rigk_estimate_start): the pixels go through the inverse of the handle's
+        pixel model at its START intrinsics (set_intrinsics / set_camera_intrinsics) first; a pixel without a root makes its view
+        invalid. Same arguments and report; the intrinsics are not written."""
+        return self._estimate_start(lib().cc_rigk_estimate_start, cam_q, cam_t, frame_q, frame_t, refine_iterations)
+
+    def _estimate_start(self, call, cam_q, cam_t, frame_q, frame_t, refine_iterations):
         opt = RigStartOptions(refine_iterations=int(refine_iterations))
         rep = RigStartReport()
         parent = np.full(self.n_cams, -1, dtype=np.int32)
@@ -868,8 +877,7 @@ class RigProblem:
                 a = _f64(a)
                 assert a.size == n
             arrs.append(a)
-        _check(lib().cc_rig_estimate_start(self._h, C.byref(opt), *[_p(a, C.c_double) if a is not None else None for a in arrs],
-                                           C.byref(rep)))
+        _check(call(self._h, C.byref(opt), *[_p(a, C.c_double) if a is not None else None for a in arrs], C.byref(rep)))
         out = {k: int(getattr(rep, k)) for k, _ in RigStartReport._fields_ if k != "parent"}
         out["parent"] = parent
         return out
@@ -886,6 +894,14 @@ class RigProblem:
         _check(lib().cc_rig_start_views(self._h, C.byref(nn), _p(cam, C.c_int32), _p(frame, C.c_int64), _p(kind, C.c_int32),
                                         _p(q, C.c_double), _p(t, C.c_double), _p(rms2, C.c_double)))
         return dict(camera=cam, frame=frame, kind=kind, q=q, t=t, rms2=rms2)
+
+    def start_points(self):
+        """(uv [n_obs, 2] float32, n_without_root): the normalised image points the last estimate_start_pixels used, in the
+        caller's observation order (NaN, NaN: no root), and how many of them are NaN (cc_rigk_start_points)."""
+        uv = np.zeros((self.n_obs, 2), dtype=np.float32)
+        bad = C.c_int64(0)
+        _check(lib().cc_rigk_start_points(self._h, _p(uv, C.c_float), C.byref(bad)))
+        return uv, int(bad.value)
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))
@@ -966,6 +982,32 @@ def rig_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, c
                                  _p(frame_q, C.c_double), _p(frame_t, C.c_double), C.c_double(huber_a),
                                  _p(cost, C.c_double), C.byref(s)))
     return cam_q, cam_t, frame_q, frame_t, cost, _summary_dict(s, log)
+
+
+def rigk_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, world_xyz, cam_frozen, intr, const_mask=0, model=MODEL_RADTAN,
+                  per_camera=False, cam_q=None, cam_t=None, frame_q=None, frame_t=None, huber_a=0.0, options=None, device=0,
+                  log_capacity=2048):
+    """Start, then solve, for the rig problem with intrinsics: a with_intrinsics handle (per_camera: one set per camera), its
+    model, intr ([9], or [n_cams, 9] per camera) and const_mask (one, or one per camera) as the start intrinsics,
+    estimate_start_pixels with the pose arrays as the caller's poses (None: the identity), solve. Returns
+    (intr, cam_q, cam_t, frame_q, frame_t, obs_cost, summary, report); intr is [9], or [n_cams, 9] per camera."""
+    p = RigProblem(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, world_xyz, cam_frozen, huber_a=huber_a, device=device,
+                   with_intrinsics="per_camera" if per_camera else True)
+    try:
+        p.set_model(model)
+        intr = _f64(intr)
+        if per_camera and intr.ndim == 2:
+            masks = np.broadcast_to(np.asarray(const_mask, dtype=np.int64), (n_cams,))
+            for c in range(n_cams):
+                p.set_camera_intrinsics(c, intr[c], int(masks[c]))
+        else:
+            p.set_intrinsics(intr, int(const_mask))
+        report = p.estimate_start_pixels(cam_q, cam_t, frame_q, frame_t)
+        summary = p.solve(options, log_capacity=log_capacity)
+        out = p.get_camera_intrinsics() if per_camera else p.get_intrinsics()
+        return (out,) + p.get_state() + (summary, report)
+    finally:
+        p.close()
 
 
 def zhang_init(frame_offsets, uv, xyz, device=0, want_homographies=False):

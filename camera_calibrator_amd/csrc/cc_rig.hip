@@ -49,6 +49,7 @@
 #include "cc_rig_inner.hpp"
 #include "cc_rig_fisheye.hpp"
 #include "cc_rig_start.hpp"
+#include "cc_rigk_start.hpp"
 #include "cc_rig_tree.hpp"
 
 namespace cc {
@@ -371,6 +372,9 @@ struct cc_rig : cc::SolveHost {   // pinned: host_pub = h_ctl's block, [20] fail
   bool st_alloc = false, st_views = false;   // ... and whether a call has filled the view records (cc_rig_start_views)
   int32_t* st_edges = nullptr;     // same memory as st.edges / st.placed
   uint8_t* st_placed = nullptr;
+  // ... of a handle with intrinsics, from its pixels (cc_rigk_estimate_start; cc_rigk_start.hpp)
+  float* st_points = nullptr;      // [N] float2 normalised points of the last pixel start, allocated by the first call
+  bool st_have_points = false;     // a pixel start has filled them (cc_rigk_start_points)
 };
 
 namespace cc {
@@ -1874,17 +1878,30 @@ extern "C" {
 
 void cc_rig_start_options_init(cc_rig_start_options* o) { if (o) o->refine_iterations = 10; }
 
-int cc_rig_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t, const double* frame_q,
-                          const double* frame_t, cc_rig_start_report* report) {
+}  // extern "C"
+
+// The start of both entry points (`who` names the caller in the messages). pixels: the handle's observations go through
+// k_rigk_start_unproject first and the start reads its output; otherwise the start reads the handle's observations themselves.
+static int rig_start_run(cc_rig* h, const char* who, bool pixels, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t,
+                         const double* frame_q, const double* frame_t, cc_rig_start_report* report) {
   using namespace cc;
-  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_estimate_start: NULL handle");
-  if (h->d.kmode) return fail(CC_ERR_STATE, "cc_rig_estimate_start: a cc_rigk_* handle holds pixel observations (the start needs normalised image points)");
-  if (h->exchange || h->comm) return fail(CC_ERR_STATE, "cc_rig_estimate_start: one device only (the handle has an exchange or a communicator)");
-  if (h->d.CO < 1 || h->NG < 1) return fail(CC_ERR_STATE, "cc_rig_estimate_start: no camera is observed");
+  if (h->exchange || h->comm) return fail(CC_ERR_STATE, "%s: one device only (the handle has an exchange or a communicator)", who);
+  if (h->d.CO < 1 || h->NG < 1) return fail(CC_ERR_STATE, "%s: no camera is observed", who);
   const int iters = opt ? opt->refine_iterations : 10;
-  if (iters < 0 || iters > 1000) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_estimate_start: refine_iterations must be in 0 .. 1000");
+  if (iters < 0 || iters > 1000) return fail(CC_ERR_BAD_ARGUMENT, "%s: refine_iterations must be in 0 .. 1000", who);
   CC_HIP(hipSetDevice(h->device));
   if (int rc = rig_start_alloc(h)) return rc;
+  if (pixels) {
+    if (!h->st_points) {   // (once per handle)
+      if (int rc = dev_alloc(h, &h->st_points, (size_t)h->N * 2)) return rc;
+    }
+    const RigDev& d = h->d;
+    h->st_have_points = false;
+    rigk_start_enqueue_unproject(RigkStartDev{h->NG, (int32_t)h->model, d.uv, d.goff, d.gcam, d.kset, h->init_intr, h->st_points}, h->stream);
+    CC_HIP(hipGetLastError());
+    h->st.uv = h->st_points;
+    h->st_have_points = true;
+  }
   const int64_t C = h->C, F = h->F, NG = h->NG;
   // stages V and R; the kinds come back for the tree
   h->st_views = false;
@@ -1946,6 +1963,52 @@ int cc_rig_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const doub
     if (report->parent) for (int64_t c = 0; c < C; ++c) report->parent[c] = tree.parent[(size_t)c];
   }
   return cc_rig_reset(h);
+}
+
+extern "C" {
+
+int cc_rig_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t, const double* frame_q,
+                          const double* frame_t, cc_rig_start_report* report) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_estimate_start: NULL handle");
+  if (h->d.kmode) return fail(CC_ERR_STATE, "cc_rig_estimate_start: a cc_rigk_* handle holds pixel observations (the start needs normalised image points: cc_rigk_estimate_start)");
+  return rig_start_run(h, "cc_rig_estimate_start", false, opt, cam_q, cam_t, frame_q, frame_t, report);
+}
+
+// EXTENSION: the same start for a handle with intrinsics, from its pixels and its start intrinsics (cc_rigk_start.hpp)
+int cc_rigk_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t, const double* frame_q,
+                           const double* frame_t, cc_rig_start_report* report) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_estimate_start: NULL handle");
+  if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_estimate_start: the handle was created without intrinsics (cc_rig_create: its observations are normalised image points, cc_rig_estimate_start)");
+  if (!h->have_intr) return fail(CC_ERR_STATE, "cc_rigk_estimate_start: cc_rigk_set_intrinsics has not been called (or not since cc_rigk_set_model changed the model): the pixels need the start intrinsics");
+  return rig_start_run(h, "cc_rigk_estimate_start", true, opt, cam_q, cam_t, frame_q, frame_t, report);
+}
+
+int cc_rigk_start_points(cc_rig* h, float* uv_normalised, int64_t* n_without_root) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_start_points: NULL handle");
+  if (!h->st_have_points) return fail(CC_ERR_STATE, "cc_rigk_start_points: cc_rigk_estimate_start has not run on this handle");
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  std::vector<float> sorted((size_t)h->N * 2);
+  if (h->N > 0) CC_HIP(hipMemcpy(sorted.data(), h->st_points, sorted.size() * sizeof(float), hipMemcpyDeviceToHost));
+  int64_t bad = 0;
+  for (int64_t i = 0; i < h->N; ++i) bad += (sorted[(size_t)2 * i] != sorted[(size_t)2 * i]) ? 1 : 0;   // (NaN comes in pairs)
+  if (n_without_root) *n_without_root = bad;
+  if (uv_normalised) {
+    if (h->perm_inverse) {   // (a handle made from columns: positions inside the frame)
+      const int32_t* rel = reinterpret_cast<const int32_t*>(h->perm.data());
+      for (int64_t f = 0; f < h->F; ++f) {
+        const int64_t a = h->goff_h[(size_t)h->fgoff_h[(size_t)f]], b = h->goff_h[(size_t)h->fgoff_h[(size_t)f + 1]];
+        for (int64_t i = a; i < b; ++i) for (int j = 0; j < 2; ++j) uv_normalised[2 * i + j] = sorted[(size_t)2 * (a + rel[i]) + j];
+      }
+    } else {
+      const int64_t* perm = h->perm.data();
+      for (int64_t i = 0; i < h->N; ++i) for (int j = 0; j < 2; ++j) uv_normalised[2 * perm[i] + j] = sorted[(size_t)2 * i + j];
+    }
+  }
+  return CC_OK;
 }
 
 int cc_rig_start_views(cc_rig* h, int64_t* n_views, int32_t* view_cam, int64_t* view_frame, int32_t* kind, double* q, double* t, double* rms2) {

@@ -472,7 +472,8 @@ int cc_rig_eval(cc_rig* h, double* cost);
  * cc_rig_start_views reads back stages V and R of the last call, one entry per view in (frame, camera) order: n_views first
  * (the other outputs may be NULL; they hold n_views entries, q 4 and t 3 doubles each), kind 0 invalid / 1 planar / 2 general,
  * rms2 = mean squared residual per observation coordinate.
- * CC_ERR_STATE, the handle unchanged: a cc_rigk_* handle (pixel observations need the lens model first), a handle with an
+ * CC_ERR_STATE, the handle unchanged: a cc_rigk_* handle (pixel observations need the lens model first: cc_rigk_estimate_start
+ * below), a handle with an
  * exchange or a communicator, a handle none of whose cameras is observed. */
 typedef struct cc_rig_start_options {
   int32_t refine_iterations;   /* default 10 */
@@ -540,6 +541,28 @@ int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9);
  * CC_ERR_BAD_ARGUMENT: an unknown model. */
 int cc_rigk_set_model(cc_rig* h, int32_t model);
 int cc_rigk_get_model(cc_rig* h, int32_t* model);
+/* EXTENSION: cc_rig_estimate_start for a cc_rigk_* handle, whose observations are pixels. Every pixel first goes through the
+ * inverse of the handle's pixel model at the handle's START intrinsics -- what cc_rigk_set_intrinsics / _set_camera_intrinsics
+ * last wrote, not what a solve has made of them -- on the device, in double precision, into a float normalised image point;
+ * stages V, R, T, C and F above then run on those points unchanged. Arguments, options, report and the meaning of the caller's
+ * poses are those of cc_rig_estimate_start; the result becomes the handle's state (cc_rig_reset returns to it), the intrinsics,
+ * their masks and the model are not written, and cc_rig_start_views reads the views back as after cc_rig_estimate_start.
+ *   radial-tangential: the root of the distortion map by damped Newton steps from the distorted point (the method of
+ *     cc_undistort, at most 100 steps); a search that does not end on a root of the map gives no point
+ *   fisheye: theta in [0, pi/2) with theta_d(theta) = |distorted point| by the rule of cc_undistort_fisheye, the point scaled
+ *     by tan(theta) / theta_d; a polynomial that turns back before it reaches the pixel gives no point; the axis maps to itself
+ * A pixel without a point (no root, a non-finite pixel, a zero or non-finite fx / fy) becomes NaN, NaN and makes its view
+ * INVALID, as a non-finite coordinate does in cc_rig_estimate_start: single observations are not dropped. Intrinsics under which
+ * no view is valid are not an error: CC_OK, every pose keeps the caller's value, the report counts the views as invalid.
+ * The pinhole form x / z of the normalised point limits the start to points well inside 90 degrees off the axis (README).
+ * cc_rigk_start_points: the normalised points of the last cc_rigk_estimate_start in the CALLER's observation order (2 floats
+ * per observation) and how many of them are NaN; either output may be NULL.
+ * CC_ERR_STATE, the handle unchanged: a poses-only handle (cc_rig_create: use cc_rig_estimate_start), no intrinsics set (never,
+ * or not since cc_rigk_set_model changed the model), a handle with an exchange or a communicator, a handle none of whose
+ * cameras is observed; cc_rigk_start_points before a start has run. cc_rig_estimate_start keeps refusing cc_rigk_* handles. */
+int cc_rigk_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t,
+                           const double* frame_q, const double* frame_t, cc_rig_start_report* report);
+int cc_rigk_start_points(cc_rig* h, float* uv_normalised, int64_t* n_without_root);
 
 /* One-shot: the call ExtrinsicsCalibrator::Optimize makes in place of
  * extrinsics_calibrator.cpp:92-225. opt == NULL -> cc_options_init with max_iterations = 1000. */
