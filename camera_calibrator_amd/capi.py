@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "cc_rig_create", "cc_rig_destroy", "cc_rig_set_state", "cc_rig_reset", "cc_rig_solve",
     "cc_rig_get_state", "cc_rig_solver_form", "cc_rig_solver_status", "cc_rig_eval", "cc_rig_optimize", "cc_rig_comm_init", "cc_rig_exchange_export", "cc_rig_exchange_attach", "cc_rigk_create",
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
-    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_rigk_estimate_start", "cc_rigk_start_points", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
+    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_rigk_set_camera_model", "cc_rigk_get_camera_model", "cc_rigk_estimate_start", "cc_rigk_start_points", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
     "cc_rig_start_options_init", "cc_rig_estimate_start", "cc_rig_start_views", "cc_rig_estimate",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
@@ -98,6 +98,7 @@ EXPORTED_SYMBOLS = [
 ]
 # EXTENSION: camera models of the single-camera solve (cc_solver.h)
 MODEL_RADTAN, MODEL_FISHEYE = 0, 1
+MODEL_MIXED = 2   # what RigProblem.get_model reports when the cameras differ (set_camera_model); never an argument
 # every symbol include/cc_harness.h declares (synthetic-input harness, host code)
 HARNESS_SYMBOLS = [
     "cc_generator_create", "cc_generator_destroy", "cc_generator_set_k", "cc_generator_set_distortion",
@@ -792,6 +793,20 @@ class RigProblem:
         _check(lib().cc_rigk_get_model(self._h, C.byref(out)))
         return int(out.value)
 
+    def set_camera_model(self, camera, model):
+        """The pixel model of ONE camera of a with_intrinsics="per_camera" handle (cc_rigk_set_camera_model). A change drops
+        that camera's intrinsics only: set_camera_intrinsics(camera, ...) again before the next solve. get_model then reports
+        MODEL_MIXED when the cameras differ."""
+        _check(lib().cc_rigk_set_camera_model(self._h, C.c_int64(camera), C.c_int32(model)))
+
+    def get_camera_model(self, camera=None):
+        """One camera's model, or (camera=None) the list of all of them (cc_rigk_get_camera_model)."""
+        if camera is None:
+            return [self.get_camera_model(c) for c in range(self.n_cams)]
+        out = C.c_int32(0)
+        _check(lib().cc_rigk_get_camera_model(self._h, C.c_int64(camera), C.byref(out)))
+        return int(out.value)
+
     def get_camera_intrinsics(self, camera=None):
         """One camera's set, or (camera=None) an [n_cams, 9] array of all of them."""
         if camera is None:
@@ -988,13 +1003,25 @@ def rigk_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, worl
                   per_camera=False, cam_q=None, cam_t=None, frame_q=None, frame_t=None, huber_a=0.0, options=None, device=0,
                   log_capacity=2048):
     """Start, then solve, for the rig problem with intrinsics: a with_intrinsics handle (per_camera: one set per camera), its
-    model, intr ([9], or [n_cams, 9] per camera) and const_mask (one, or one per camera) as the start intrinsics,
+    model (one, or with per_camera a sequence of n_cams: set_camera_model, applied before the intrinsics), intr ([9], or
+    [n_cams, 9] per camera) and const_mask (one, or one per camera) as the start intrinsics,
     estimate_start_pixels with the pose arrays as the caller's poses (None: the identity), solve. Returns
     (intr, cam_q, cam_t, frame_q, frame_t, obs_cost, summary, report); intr is [9], or [n_cams, 9] per camera."""
+    models = None
+    if not np.isscalar(model):
+        models = [int(m) for m in model]
+        if not per_camera:
+            raise ValueError("rigk_estimate: a model per camera needs per_camera=True (one shared set cannot follow two models)")
+        if len(models) != n_cams:
+            raise ValueError("rigk_estimate: %d models for %d cameras" % (len(models), n_cams))
     p = RigProblem(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, world_xyz, cam_frozen, huber_a=huber_a, device=device,
                    with_intrinsics="per_camera" if per_camera else True)
     try:
-        p.set_model(model)
+        if models is None:
+            p.set_model(model)
+        else:
+            for c, m in enumerate(models):
+                p.set_camera_model(c, m)
         intr = _f64(intr)
         if per_camera and intr.ndim == 2:
             masks = np.broadcast_to(np.asarray(const_mask, dtype=np.int64), (n_cams,))

@@ -14,6 +14,9 @@
 //   k_rig_sweep_k2     extension (intrinsics): 16-column Gram on plain FMAs, two waves per group, compact records
 //   k_rig_sweep_adjk   extension, tiles (large rigs; CC_RIG_K_COMPACT=0)
 //   k_rig_sweep_adjk_fisheye   extension, tiles, the fisheye pixel model (cc_rigk_set_model; a unit of its own: cc_rig_fisheye.hip)
+//   k_rig_sweep_adjk_sel       extension, tiles, a pixel model per camera (cc_rigk_set_camera_model; cc_rig_mixed.hip): ONE LAUNCH PER
+//                              MODEL that has a group, so under profile_kernels a sweep of a mixed handle counts two launches of
+//                              CC_K_SWEEP in kernel_launches while `sweeps` of the summary stays one per round
 // (The first formulation -- every row's 13 / 22 columns through the matrix pipe, k_rig_sweep -- lost to the adjoint forms in
 // round 2 and was deleted in round 5; git history has it.) Only cameras that are
 // observed AND not frozen own columns of the reduced system (any number of frozen / unobserved cameras
@@ -48,6 +51,7 @@
 #include "cc_rig_dev.hpp"
 #include "cc_rig_inner.hpp"
 #include "cc_rig_fisheye.hpp"
+#include "cc_rig_mixed.hpp"
 #include "cc_rig_start.hpp"
 #include "cc_rigk_start.hpp"
 #include "cc_rig_tree.hpp"
@@ -315,7 +319,13 @@ struct cc_rig : cc::SolveHost {   // pinned: host_pub = h_ctl's block, [20] fail
   bool frame_allowed = true; // poses-only, three-kernel path: the FRAME form of the sweep (k_rig_sweep_frame); CC_RIG_SWEEP_FRAME=0: one workgroup per group (k_rig_sweep_adj)
   int frame_waves = 2;       // waves per frame workgroup of the frame form
   int kmode = 0;
-  int model = CC_MODEL_RADTAN;   // cc_rigk_set_model: the pixel model of every camera of the handle (fisheye: cc_rig_fisheye.hpp, tiles only)
+  int model = CC_MODEL_RADTAN;   // cc_rigk_set_model: the pixel model of every camera of the handle (fisheye: cc_rig_fisheye.hpp, tiles only);
+                                 // CC_MODEL_MIXED when the cameras differ (cc_rigk_set_camera_model: cc_rig_mixed.hpp, tiles only)
+  std::vector<int32_t> cam_model;      // [C] the model of every camera (all equal to `model` unless that is CC_MODEL_MIXED)
+  std::vector<uint8_t> intr_dropped;   // [C] a change of this camera's model dropped its intrinsics: set them before the next solve
+  int32_t* d_cmodel = nullptr;         // [C] device copy of cam_model (a mixed handle; allocated by the first one)
+  int32_t* d_glist = nullptr;          // [NG] the groups of the radial-tangential cameras, then those of the fisheye cameras
+  int32_t nlist[2] = {0, 0};           // how many of each
   std::vector<int64_t> perm;  // sorted position -> caller's observation index
   bool perm_inverse = false;   // columns: the storage holds int32 entries, [k] = where the caller's observation k went, counted from its frame's first position -- instead of perm[i] = caller's index of position i
   std::vector<std::pair<void*, size_t>> allocs;   // the chunks dev_alloc carves buffers from (cc::pool_alloc: recycled between handles)
@@ -519,7 +529,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     const double per_group = h->NG > 0 ? (double)h->N / (double)h->NG : 0.0;
     bool on = per_group >= 448.0;
     if (const char* e = getenv("CC_RIG_K_COMPACT")) on = atoi(e) != 0;
-    d.kcm = (kmode && !h->big && on && h->model != CC_MODEL_FISHEYE) ? 1 : 0;   // (no compact-record form of the fisheye sweep)
+    d.kcm = (kmode && !h->big && on && h->model == CC_MODEL_RADTAN) ? 1 : 0;   // (no compact-record form of the fisheye sweep, nor of a mixed handle's)
   }
   d.C = (int32_t)C; d.CO = CO; d.CK = CK; d.S = S; d.SW = S + 1;
   d.T = (d.SW + 15) / 16; d.nT = d.T * (d.T + 1) / 2; d.ZS = 16 * d.T + ((d.T & 1) ? 0 : 16);
@@ -625,6 +635,19 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
       gk[(size_t)2 * g + 1] = int4{c, kset[(size_t)c], fixed[(size_t)c] ? 1 : 0, 0};
     }
     if (int rc = dev_upload(h, &d.gk2, gk)) return rc;
+  }
+  if (h->model == CC_MODEL_MIXED) {   // the cameras' models and one list of groups per model (cc_rig_mixed.hpp)
+    if (!h->d_cmodel) { if (int rc = dev_alloc(h, &h->d_cmodel, (size_t)C)) return rc; }
+    if (!h->d_glist) { if (int rc = dev_alloc(h, &h->d_glist, (size_t)h->NG)) return rc; }
+    std::vector<int32_t> gl;
+    gl.reserve((size_t)h->NG);
+    for (int m = 0; m < 2; ++m) {
+      const size_t before = gl.size();
+      for (int64_t g = 0; g < h->NG; ++g) if (h->cam_model[(size_t)h->gcam_h[(size_t)g]] == m) gl.push_back((int32_t)g);
+      h->nlist[m] = (int32_t)(gl.size() - before);
+    }
+    CC_HIP(hipMemcpy(h->d_cmodel, h->cam_model.data(), (size_t)C * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!gl.empty()) CC_HIP(hipMemcpy(h->d_glist, gl.data(), gl.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   if (!h->d_cam_fixed) { if (int rc = dev_alloc(h, &h->d_cam_fixed, (size_t)C)) return rc; d.cam_fixed = h->d_cam_fixed; }
   CC_HIP(hipMemcpy(h->d_cam_fixed, fixed.data(), fixed.size(), hipMemcpyHostToDevice));
@@ -804,6 +827,9 @@ static RigFishDev rig_fish_dev(const cc_rig* h) {
   return RigFishDev{d.F, d.NG, d.C, d.CK, d.uv, d.oxyz, d.widx, d.wxyz, d.goff, d.gframe, d.gcam, d.cam_fixed, d.kset, d.kmask, d.cam, d.pose,
                     d.intr, d.camrec, d.frec, d.krec, d.gblocks, d.gstats, d.ghd0, d.ghdk, d.gcomp, d.ctl, d.gstride, d.huber_a, d.huber_b, d.huber_2a};
 }
+static RigMixedDev rig_mixed_dev(const cc_rig* h) {
+  return RigMixedDev{rig_fish_dev(h), h->d_cmodel, {h->d_glist, h->d_glist + h->nlist[0]}, {h->nlist[0], h->nlist[1]}};
+}
 static RigInnerDev rig_inner_dev(const cc_rig* h) {
   const RigDev& d = h->d;
   return RigInnerDev{d.F, d.NG, d.C, d.fmode, d.uv, d.oxyz, d.goff, d.gframe, d.gcam, d.fgoff, d.cam_goff, d.cam_glist, d.pcol,
@@ -842,7 +868,11 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     else if (h->sweep_waves == 2) hipLaunchKernelGGL((k_rig_sweep_adj<2>), dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);
     else hipLaunchKernelGGL((k_rig_sweep_adj<1>), dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
   };
-  { Probe p(h, CC_K_SWEEP, profile); sweep(); }
+  if (h->model == CC_MODEL_MIXED) {   // one launch per model that has a group, one after the other; each a CC_K_SWEEP of its own when profiled
+    const RigMixedDev M = rig_mixed_dev(h);
+    for (int m = 0; m < 2; ++m)
+      if (M.nlist[m] > 0) { Probe p(h, CC_K_SWEEP, profile); rig_mixed_enqueue_sweep(M, h->stream, h->sweep_waves, m); }
+  } else { Probe p(h, CC_K_SWEEP, profile); sweep(); }
   if (h->inner_on && !initial && !h->comm && !h->exchange) {
     // inner iterations (cc_rig_inner.hpp): a pass on the candidate, the sweep again at its result, the decision with the
     // augmented model. Every launch returns at once in a round without a pass; none is probed (kept out of kernel_ms).
@@ -1146,6 +1176,8 @@ static int rig_create_impl(int32_t device, int64_t C, int64_t F, int64_t n_world
     for (int64_t g = 0; g < NG; ++g) cam_glist[(size_t)fill[gcam[g]]++] = (int32_t)g;
   }
   h->frozen.assign((size_t)C, 0);
+  h->cam_model.assign((size_t)C, CC_MODEL_RADTAN);
+  h->intr_dropped.assign((size_t)C, 0);
   if (cam_frozen) for (int64_t c = 0; c < C; ++c) h->frozen[(size_t)c] = cam_frozen[c] ? 1 : 0;
   h->seen = seen;
   hp.mark("gather");
@@ -1315,14 +1347,22 @@ static int rigk_set(cc_rig* h, int64_t camera, const double* intr9, uint32_t con
   CC_HIP(hipStreamSynchronize(h->stream));
   double k16[16] = {0};
   for (int i = 0; i < 9; ++i) k16[i] = intr9[i];
-  uint32_t m = const_mask & 0x1ffu;
-  if (h->model == CC_MODEL_FISHEYE) { m |= 1u << 8; k16[8] = 0.0; }   // slot 8 is not part of the model: held, stored as 0 (cc_intrinsics_set_state)
+  const uint32_t m = const_mask & 0x1ffu;
   for (int s = 0; s < CK; ++s) {
     if (camera >= 0 && s != camera) continue;
-    CC_HIP(hipMemcpy(h->init_intr + (size_t)s * 16, k16, sizeof(k16), hipMemcpyHostToDevice));
-    CC_HIP(hipMemcpy(h->d_kmask + s, &m, sizeof(m), hipMemcpyHostToDevice));
+    // a fisheye set (a set's cameras share their model): slot 8 is not part of the model: held, stored as 0 (cc_intrinsics_set_state)
+    const bool fish = h->cam_model[(size_t)s] == CC_MODEL_FISHEYE;
+    const uint32_t ms = fish ? (m | (1u << 8)) : m;
+    double ks16[16];
+    for (int i = 0; i < 16; ++i) ks16[i] = k16[i];
+    if (fish) ks16[8] = 0.0;
+    CC_HIP(hipMemcpy(h->init_intr + (size_t)s * 16, ks16, sizeof(ks16), hipMemcpyHostToDevice));
+    CC_HIP(hipMemcpy(h->d_kmask + s, &ms, sizeof(ms), hipMemcpyHostToDevice));
+    if (h->d.kmode == RIG_K_PER_CAMERA) h->intr_dropped[(size_t)s] = 0;
   }
+  if (h->d.kmode != RIG_K_PER_CAMERA) std::fill(h->intr_dropped.begin(), h->intr_dropped.end(), 0);
   h->have_intr = true;
+  for (uint8_t dr : h->intr_dropped) if (dr) h->have_intr = false;   // (a camera whose model changed still waits for its set)
   return h->have_state ? cc_rig_reset(h) : CC_OK;
 }
 
@@ -1360,6 +1400,8 @@ int cc_rigk_set_model(cc_rig* h, int32_t model) {
   CC_HIP(hipSetDevice(h->device));
   CC_HIP(hipStreamSynchronize(h->stream));
   h->model = model;
+  std::fill(h->cam_model.begin(), h->cam_model.end(), model);
+  std::fill(h->intr_dropped.begin(), h->intr_dropped.end(), 0);
   h->have_intr = false;   // the slots mean something else: cc_rigk_set_intrinsics again
   const std::vector<uint8_t> any = h->seen_any;
   return rig_layout(h, any);   // (tile form for the fisheye model; drops the captured graphs)
@@ -1369,6 +1411,40 @@ int cc_rigk_get_model(cc_rig* h, int32_t* model) {
   if (!h || !model) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_get_model: NULL argument");
   if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_get_model: the handle was created without intrinsics (cc_rig_create)");
   *model = h->model;
+  return CC_OK;
+}
+
+// EXTENSION: the pixel model of ONE camera of a handle with a set of intrinsics per camera (cc_rig_mixed.hpp)
+int cc_rigk_set_camera_model(cc_rig* h, int64_t camera, int32_t model) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_camera_model: NULL handle");
+  if (model == CC_MODEL_MIXED) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_camera_model: CC_MODEL_MIXED is what cc_rigk_get_model reports, not a model of a camera");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_camera_model: unknown model %d", (int)model);
+  if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_set_camera_model: the handle was created without intrinsics (cc_rig_create)");
+  if (h->d.kmode != RIG_K_PER_CAMERA)
+    return fail(CC_ERR_STATE, "cc_rigk_set_camera_model: the handle has one set of intrinsics for all cameras (cc_rigk_create), which cannot follow two models: use cc_rigk_set_model, or cc_rigk_create_per_camera");
+  if (camera < 0 || camera >= h->C) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_camera_model: camera %lld out of range (the handle has %lld)", (long long)camera, (long long)h->C);
+  if (model == h->cam_model[(size_t)camera]) return CC_OK;
+  if (model == CC_MODEL_FISHEYE && (h->comm || h->exchange || h->mailbox.local))
+    return fail(CC_ERR_STATE, "cc_rigk_set_camera_model: the fisheye model runs on one device only (the handle has an exchange or a communicator attached)");
+  CC_HIP(hipSetDevice(h->device));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  h->cam_model[(size_t)camera] = model;
+  h->model = model;
+  for (int32_t cm : h->cam_model) if (cm != model) h->model = CC_MODEL_MIXED;
+  h->intr_dropped[(size_t)camera] = 1;   // this camera's slots mean something else: cc_rigk_set_camera_intrinsics again
+  h->have_intr = false;
+  const std::vector<uint8_t> any = h->seen_any;
+  return rig_layout(h, any);   // (tile form unless every camera is radial-tangential; the group lists; drops the captured graphs)
+}
+int cc_rigk_get_camera_model(cc_rig* h, int64_t camera, int32_t* model) {
+  using namespace cc;
+  if (!h || !model) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_get_camera_model: NULL argument");
+  if (!h->d.kmode) return fail(CC_ERR_STATE, "cc_rigk_get_camera_model: the handle was created without intrinsics (cc_rig_create)");
+  if (h->d.kmode != RIG_K_PER_CAMERA)
+    return fail(CC_ERR_STATE, "cc_rigk_get_camera_model: the handle has one set of intrinsics for all cameras (cc_rigk_create): its model is cc_rigk_get_model's");
+  if (camera < 0 || camera >= h->C) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_get_camera_model: camera %lld out of range (the handle has %lld)", (long long)camera, (long long)h->C);
+  *model = h->cam_model[(size_t)camera];
   return CC_OK;
 }
 
@@ -1794,6 +1870,7 @@ int cc_rig_get_state(cc_rig* h, double* cam_q, double* cam_t, double* frame_q, d
   }
   if (obs_cost && h->N > 0) {
     if (h->model == CC_MODEL_FISHEYE) rig_fisheye_enqueue_obs_cost(rig_fish_dev(h), h->stream, cur, h->d_cost);
+    else if (h->model == CC_MODEL_MIXED) rig_mixed_enqueue_obs_cost(rig_mixed_dev(h), h->stream, cur, h->d_cost);
     else hipLaunchKernelGGL(k_rig_obs_cost, dim3((unsigned)h->NG), dim3(256), 0, h->stream, h->d, cur, h->d_cost);
     CC_HIP(hipGetLastError());
     // through the cached pinned block (full PCIe rate, no fresh 8N-byte vector to fault in), back into the caller's order on
@@ -1897,7 +1974,8 @@ static int rig_start_run(cc_rig* h, const char* who, bool pixels, const cc_rig_s
     }
     const RigDev& d = h->d;
     h->st_have_points = false;
-    rigk_start_enqueue_unproject(RigkStartDev{h->NG, (int32_t)h->model, d.uv, d.goff, d.gcam, d.kset, h->init_intr, h->st_points}, h->stream);
+    if (h->model == CC_MODEL_MIXED) rigk_start_enqueue_unproject_cam(RigkStartCamDev{h->NG, h->d_cmodel, d.uv, d.goff, d.gcam, d.kset, h->init_intr, h->st_points}, h->stream);
+    else rigk_start_enqueue_unproject(RigkStartDev{h->NG, (int32_t)h->model, d.uv, d.goff, d.gcam, d.kset, h->init_intr, h->st_points}, h->stream);
     CC_HIP(hipGetLastError());
     h->st.uv = h->st_points;
     h->st_have_points = true;
@@ -2056,7 +2134,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
   using namespace cc;
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_comm_init: bad arguments (nranks must be 1..32)");
-  if (h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has the fisheye model (one device only: cc_rigk_set_model)");
+  if (h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has the fisheye model, for all or some of its cameras (one device only: cc_rigk_set_model, cc_rigk_set_camera_model)");
   if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_comm_init: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   CC_HIP(hipSetDevice(h->device));
   if (h->comm) { comm_destroy(h->comm); h->comm = nullptr; }
@@ -2080,7 +2158,7 @@ int cc_rig_comm_init(cc_rig* h, const uint8_t id[128], int32_t rank, int32_t nra
 
 int cc_rig_exchange_export(cc_rig* h, uint8_t handle[64]) {
   using namespace cc;
-  if (h && h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_exchange_export: the handle has the fisheye model (one device only: cc_rigk_set_model)");
+  if (h && h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_rig_exchange_export: the handle has the fisheye model, for all or some of its cameras (one device only: cc_rigk_set_model, cc_rigk_set_camera_model)");
   if (int rc = exchange_export_begin(h, handle, "cc_rig_exchange_export")) return rc;
   h->d.x = P2pDev{};
   int k0 = 0, k1 = 0;
@@ -2093,7 +2171,7 @@ int cc_rig_exchange_attach(cc_rig* h, int32_t rank, int32_t nranks, const uint8_
   using namespace cc;
   if (!h || !handles || rank < 0 || nranks < 1 || rank >= nranks || nranks > kP2pMaxRanks)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_rig_exchange_attach: bad arguments (nranks must be 1..%d)", kP2pMaxRanks);
-  if (h->model == CC_MODEL_FISHEYE) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has the fisheye model (one device only: cc_rigk_set_model)");
+  if (h->model != CC_MODEL_RADTAN) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has the fisheye model, for all or some of its cameras (one device only: cc_rigk_set_model, cc_rigk_set_camera_model)");
   if (!h->mailbox.local) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: call cc_rig_exchange_export first");
   if (h->inner_on) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: the handle has inner iterations on (one device only: cc_rig_set_inner_iterations(h, 0, ..) first)");
   if (h->comm) return fail(CC_ERR_STATE, "cc_rig_exchange_attach: an RCCL communicator is already attached");

@@ -529,7 +529,8 @@ int cc_rigk_create_per_camera(int32_t device, int64_t n_cams, int64_t n_frames, 
 int cc_rigk_set_camera_intrinsics(cc_rig* h, int64_t camera, const double* intr9, uint32_t const_mask);
 int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9);
 /* EXTENSION: the pixel model of a cc_rigk_* handle (CC_MODEL_RADTAN, the default, or CC_MODEL_FISHEYE, above). The model
- * belongs to the handle, for all of its cameras -- one shared set or one per camera; a rig that mixes both is out of scope.
+ * belongs to the handle, for all of its cameras -- one shared set or one per camera; a rig that mixes both gives each camera
+ * its own (cc_rigk_set_camera_model below).
  * Fisheye: the slots are fx fy px py k1 k2 k3 k4 -; cc_rigk_set_intrinsics / _set_camera_intrinsics force bit 8 of the
  * constant mask and store 0 in slot 8. A CHANGE of the model drops the captured graphs and the intrinsics (the next solve
  * needs cc_rigk_set_intrinsics again) and puts the handle on the tile form of the sweep (k_rig_sweep_adjk_fisheye: there is
@@ -541,6 +542,29 @@ int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9);
  * CC_ERR_BAD_ARGUMENT: an unknown model. */
 int cc_rigk_set_model(cc_rig* h, int32_t model);
 int cc_rigk_get_model(cc_rig* h, int32_t* model);
+/* EXTENSION: a pixel model PER CAMERA, for a handle with a set of intrinsics per camera (cc_rigk_create_per_camera): a fisheye
+ * lens next to radial-tangential ones, refined jointly over the frame poses they share. cc_rigk_get_model reports
+ * CC_MODEL_MIXED when the cameras differ, otherwise their common model; CC_MODEL_MIXED is never accepted as an argument.
+ * Setting the model a camera has is a no-op. A CHANGE drops the captured graphs and THAT camera's intrinsics only -- the other
+ * sets and all poses stay; a solve, eval or start before that camera's next cc_rigk_set_camera_intrinsics (or
+ * cc_rigk_set_intrinsics) fails with CC_ERR_STATE. A fisheye camera's set has the slots fx fy px py k1 k2 k3 k4 -:
+ * cc_rigk_set_camera_intrinsics forces bit 8 of THAT set's constant mask and stores 0 in its slot 8, a radial-tangential
+ * camera's set is taken as given; cc_rigk_set_intrinsics applies the rule set by set. cc_rigk_set_model keeps its meaning on
+ * such a handle: every camera gets the model (a no-op when every camera has it, otherwise all intrinsics are dropped).
+ * A handle all of whose cameras have one model IS the homogeneous handle of that model, however it got there: it launches the
+ * kernels such a handle launches and returns the same bits. A handle whose cameras differ sweeps into tiles (no compact-record
+ * form, whatever the group size and CC_RIG_K_COMPACT) with ONE LAUNCH PER MODEL that has an observed camera
+ * (k_rig_sweep_adjk_sel): under profile_kernels a sweep then counts two launches of CC_K_SWEEP in kernel_launches while
+ * `sweeps` stays one per round. Large rigs, cc_rig_eval / _reset / _solver_status / _get_state, profiled rounds and
+ * cc_rigk_estimate_start (every pixel through the inverse of ITS camera's model) work. A camera without observations keeps
+ * its recorded model.
+ * CC_ERR_STATE, the handle unchanged: a poses-only handle (cc_rig_create); a handle with one shared set (cc_rigk_create: one
+ * set of nine numbers cannot follow two models, use cc_rigk_set_model); CC_MODEL_FISHEYE on a handle with an exchange or a
+ * communicator (and cc_rig_comm_init / cc_rig_exchange_export / _attach on a handle ANY camera of which is fisheye).
+ * CC_ERR_BAD_ARGUMENT, the handle unchanged: a camera out of range, an unknown model, CC_MODEL_MIXED, a NULL output. */
+enum { CC_MODEL_MIXED = 2 };   /* reported only, never accepted as an argument */
+int cc_rigk_set_camera_model(cc_rig* h, int64_t camera, int32_t model);
+int cc_rigk_get_camera_model(cc_rig* h, int64_t camera, int32_t* model);
 /* EXTENSION: cc_rig_estimate_start for a cc_rigk_* handle, whose observations are pixels. Every pixel first goes through the
  * inverse of the handle's pixel model at the handle's START intrinsics -- what cc_rigk_set_intrinsics / _set_camera_intrinsics
  * last wrote, not what a solve has made of them -- on the device, in double precision, into a float normalised image point;

@@ -1,0 +1,373 @@
+"""EXTENSION: a pixel model per camera on one rig handle with intrinsics (cc_rigk_set_camera_model / _get_camera_model; the
+kernels: cc_rig_mixed.hip). The checker is tests/rigk_mixed_ref.py -- tests/rigk_fisheye_ref.py's LM on a problem whose rows come
+from each camera's own model -- itself pinned on the CPU (tests/test_rigk_mixed_cpu.py).
+
+Bounds (the project's standing ones for this path): identical termination, iteration count, accept / valid
+sequence; logged costs 1e-9 relative; fx fy px py 1e-9 relative, distortion and poses 1e-9; per-observation costs 1e-8 relative
+with atol 1e-12; the total cost of one evaluation 1e-12 relative; a group's 16 x 16 Gram 1e-12 of its largest entry. Every test
+prints what it measured (DESIGN.md 4.17 has the table). Every test calls cc_rigk_set_camera_model and fails on a library
+without it."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from camera_calibrator_amd import capi
+from tests import rigk_mixed_ref as mr
+from tests import rigk_start_ref as sref
+from tests.test_rigk_start_ref_cpu import CAM_R_ABS, CAM_T_ABS, COST_REL, INTR_REL, distances, tight_options
+
+pytestmark = pytest.mark.gpu
+CC_ERR_BAD_ARGUMENT, CC_ERR_STATE = -1, -5
+TIGHT = dict(max_iterations=1000, function_tolerance=1e-15, gradient_tolerance=1e-13, parameter_tolerance=1e-14)
+
+
+def _create(k, huber_a=0.0, kind="per_camera"):
+    return capi.RigProblem(k["cams"], k["frame_offsets"], k["obs_cam"], k["obs_world"], k["obs_uv_pix"], k["world_xyz"], k["cam_frozen"],
+                           huber_a=huber_a, with_intrinsics=kind)
+
+
+def _set_intrinsics(prob, k, const_masks=None, intr=None):
+    intr = k["intr0"] if intr is None else intr
+    for c in range(k["cams"]):
+        prob.set_camera_intrinsics(c, intr[c], 0 if const_masks is None else int(const_masks[c]))
+
+
+def _problem(k, const_masks=None, huber_a=0.0, state=True):
+    prob = _create(k, huber_a)
+    for c, m in enumerate(mr.model_ids(k["kinds"])):
+        prob.set_camera_model(c, m)
+    _set_intrinsics(prob, k, const_masks)
+    if state:
+        prob.set_state(k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"])
+    return prob
+
+
+def _state(prob, summary):
+    return (prob.get_camera_intrinsics(),) + tuple(prob.get_state()) + (summary,)
+
+
+def _gpu(name):
+    k, pk, ok = mr.gpu_case(name)
+    prob = _problem(k, **pk)
+    assert prob.get_model() == capi.MODEL_MIXED and prob.get_camera_model() == mr.model_ids(k["kinds"])
+    s = prob.solve(capi.default_options(**ok))
+    g = _state(prob, s)
+    prob.close()
+    return k, g
+
+
+def _assert_same(g, o, what):
+    sg, so = g[6], o[6]
+    assert sg["termination"] == so["termination"] and sg["iterations"] == so["iterations"], (sg["termination"], sg["iterations"], so["termination"], so["iterations"])
+    assert [l["accepted"] for l in sg["log"]] == [l["accepted"] for l in so["log"]]
+    assert [l["valid"] for l in sg["log"]] == [l["valid"] for l in so["log"]]
+    gi, oi = np.atleast_2d(g[0]), np.atleast_2d(o[0])
+    dev = dict(costs=max(abs(a["cost"] / b["cost"] - 1) for a, b in zip(sg["log"], so["log"])),
+               focal=np.abs(gi[:, :4] / oi[:, :4] - 1).max(), dist=np.abs(gi[:, 4:] - oi[:, 4:]).max(),
+               poses=max(np.abs(g[a] - o[a]).max() for a in range(1, 5)),
+               obs=(np.abs(g[5] - o[5]) / np.maximum(np.abs(o[5]), 1e-4)).max())
+    print("%s measured: " % what + ", ".join("%s %.2g" % kv for kv in dev.items()))
+    assert dev["costs"] <= 1e-9 and dev["focal"] <= 1e-9 and dev["dist"] <= 1e-9 and dev["poses"] <= 1e-9
+    assert np.allclose(g[5], o[5], rtol=1e-8, atol=1e-12)
+    return dev
+
+
+def _fetch(prob, name, n):
+    buf = np.zeros(n)
+    capi._check(capi.lib().cc_rig_debug_fetch(prob._h, name.encode(), buf.ctypes.data_as(C.POINTER(C.c_double)), C.c_int64(n)))
+    return buf
+
+
+def _bits(a, b):
+    return all(np.asarray(x).tobytes() == np.asarray(y).tobytes() for x, y in zip(a, b))
+
+
+def _log(s):
+    return [tuple(sorted(l.items())) for l in s["log"]]
+
+
+# ---- 1. solve parity ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["rf", "fr", "ng1024", "percam", "big"])
+def test_solve_matches_the_reference(name):
+    """rf / fr: one pass of the one-wave form; ng1024: 1024 groups, one wave per group, one frame of three passes; percam: masks
+    on both kinds of set, the loss with observations in its tail; big: 144 shared coordinates, the large-rig kernels."""
+    k, g = _gpu(name)
+    o = mr.gpu_reference(name)
+    _assert_same(g, o, name)
+    for c, x in enumerate(k["kinds"]):      # slot 8: 0 on a fisheye camera, the camera's k3 on a radial-tangential one
+        assert (g[0][c, 8] == 0.0) == (x == "F" or name == "percam"), (c, x, g[0][c, 8])
+    if name == "percam":
+        assert (np.sqrt(2 * o[5]) > 1.5).sum() > 50     # the tail is populated at the minimiser
+        assert np.array_equal(g[0][0, 6:8], k["intr0"][0, 6:8]) and g[0][2, 7] == k["intr0"][2, 7] and g[0][1, 8] == k["intr0"][1, 8]
+
+
+@pytest.mark.parametrize("name", ["ragged_rf", "ragged_fr"])
+def test_ragged_groups_in_both_workgroup_forms(name, monkeypatch):
+    """Two cameras x four frames cut to (frame, camera) groups of 1, 63, 64, 65, 257, 530, none and 130 observations: camera 0 has
+    the groups of 1, 64, 257 and none, camera 1 those of 63, 65, 530 and 130, and the two shapes swap the models. Four waves by
+    default (a pass is 256 observations: 530 gives the unrolled pair and the tail), one wave forced (530: nine passes)."""
+    k, pk, ok = mr.gpu_case(name)
+    assert [len(i) for _, _, i in mr.groups(k)] == [1, 63, 64, 65, 257, 530, 130]
+    ref = mr.gpu_reference(name)
+    for waves in (4, 1):
+        monkeypatch.setenv("CC_RIG_SWEEP_WG_WAVES", str(waves))
+        prob = _problem(k, **pk)
+        s = prob.solve(capi.default_options(**ok))
+        g = _state(prob, s)
+        prob.close()
+        _assert_same(g, ref, "%s, %d wave(s)" % (name, waves))
+
+
+# ---- 2. one evaluation --------------------------------------------------------------------------------------------------------
+def test_eval_on_rf():
+    k, pk, _ = mr.gpu_case("rf")
+    P = mr.problem(k, **pk)
+    st = tuple(np.asarray(a, dtype=np.longdouble) for a in (k["intr0"], k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"]))
+    want, oc, _ = P.eval(st, np.longdouble, blocks=False)
+    prob = _problem(k, **pk)
+    cost = prob.eval()
+    got_oc = prob.get_state()[4]
+    prob.close()
+    print("rf: total cost %.2g relative, per-observation costs %.2g relative" % (abs(cost / float(want) - 1), np.abs(got_oc / oc.astype(np.float64) - 1).max()))
+    assert abs(cost - float(want)) <= 1e-12 * float(want)
+    assert np.allclose(got_oc, oc.astype(np.float64), rtol=1e-8, atol=1e-12)
+
+
+# ---- 3. group Grams -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["ragged_rf", "ragged_fr"])
+def test_group_grams_of_each_model(name, monkeypatch):
+    """The 16 x 16 Gram of X = [J_cam(6) r J_k(9)] the sweep left for the starting point (the compact record's first 256
+    doubles) of the groups of 1 (camera 0), 65 and 530 (camera 1) observations against the np.longdouble Gram of the reference
+    rows at the same state, 1e-12 of its largest entry: over the two shapes each model has each size. A fisheye group has no
+    column for slot 8; a radial-tangential one has."""
+    k, pk, _ = mr.gpu_case(name)
+    P = mr.problem(k, **pk)
+    st = (k["intr0"], k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"])
+    groups = mr.groups(k)
+    picks = [0, 3, 5]
+    assert [len(groups[i][2]) for i in picks] == [1, 65, 530] and [groups[i][1] for i in picks] == [0, 1, 1]
+    want = {i: mr.group_gram(P, st, groups[i][2]) for i in picks}
+    for waves in (4, 1):
+        monkeypatch.setenv("CC_RIG_SWEEP_WG_WAVES", str(waves))
+        prob = _problem(k, **pk)
+        prob.solve(capi.default_options(max_iterations=1))
+        rec = _fetch(prob, "gcomp", len(groups) * 320).reshape(len(groups), 320)
+        prob.close()
+        for i in picks:
+            got, w = rec[i, :256].reshape(16, 16), want[i].astype(np.float64)
+            dev = np.abs(got - want[i]).max() / np.abs(want[i]).max()
+            kind = k["kinds"][groups[i][1]]
+            print("%s, %d wave(s), group %d (%s, %d observations): Gram deviation / largest entry %.2g" % (name, waves, i, kind, len(groups[i][2]), float(dev)))
+            assert np.all(np.isfinite(got)) and dev <= 1e-12, (i, float(dev))
+            if kind == "F":
+                assert np.array_equal(got[15], np.zeros(16)) and np.array_equal(got[:, 15], np.zeros(16))
+            else:
+                assert got[15, 15] > 0.0 and w[15, 15] > 0.0
+
+
+# ---- 4. cameras without observations --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["rrf_unseen", "ffr_unseen"])
+def test_a_model_whose_cameras_are_all_unobserved_launches_nothing(name):
+    """Camera 2, the only camera of its model, has no observation: its model's list of groups is empty and that sweep is not
+    launched (a grid of zero workgroups is a launch error). The handle is still a mixed one; the solve matches the reference,
+    no error is left behind, and an ordinary solve on a fresh handle works afterwards."""
+    before = capi.lib().cc_last_error()
+    k, g = _gpu(name)
+    _assert_same(g, mr.gpu_reference(name), name)
+    assert capi.lib().cc_last_error() == before
+    k2, pk2, ok2 = mr.gpu_case("rf")
+    prob = _problem(k2, **pk2)
+    s = prob.solve(capi.default_options(**ok2))
+    prob.close()
+    assert s["iterations"] == mr.gpu_reference("rf")[6]["iterations"] and capi.lib().cc_last_error() == before
+
+
+# ---- 5. nothing moved ---------------------------------------------------------------------------------------------------------
+def test_a_handle_whose_cameras_agree_is_the_homogeneous_handle_bit_for_bit():
+    """All cameras set to fisheye one by one = set_model(FISHEYE); radtan -> mixed -> all radtan (intrinsics set again) = a handle
+    that was never touched: state, intrinsics, per-observation costs, log and the reported form."""
+    def run(k, route, masks=None, huber_a=0.0):
+        prob = _create(k, huber_a)
+        if route == "set_model":
+            prob.set_model(capi.MODEL_FISHEYE)
+        elif route == "one by one":
+            for c in range(k["cams"]):
+                prob.set_camera_model(c, capi.MODEL_FISHEYE)
+                assert prob.get_model() == (capi.MODEL_FISHEYE if c == k["cams"] - 1 else capi.MODEL_MIXED)
+        _set_intrinsics(prob, k, masks)
+        if route == "round trip":
+            prob.set_camera_model(1, capi.MODEL_FISHEYE)
+            assert prob.get_model() == capi.MODEL_MIXED
+            prob.set_camera_model(1, capi.MODEL_RADTAN)
+            assert prob.get_model() == capi.MODEL_RADTAN
+            prob.set_camera_intrinsics(1, k["intr0"][1], 0 if masks is None else int(masks[1]))
+        prob.set_state(k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"])
+        s = prob.solve(capi.default_options(max_iterations=200))
+        out = _state(prob, s), prob.solver_status()[0]
+        prob.close()
+        return out
+
+    from camera_calibrator_amd.harness import rigk_case
+    from tests import rigk_fisheye_ref as rr
+    kf = rr.fisheye_rig_case(3, 20, 25, per_camera=True)
+    a, b = run(kf, "set_model", rr.PC_MASKS, 1.5), run(kf, "one by one", rr.PC_MASKS, 1.5)
+    assert a[0][6]["iterations"] >= 3 and _bits(a[0][:6], b[0][:6]) and _log(a[0][6]) == _log(b[0][6]) and a[1] == b[1]
+    kr = rigk_case(3, 20, 30, per_camera=True)
+    a, b = run(kr, "never"), run(kr, "round trip")
+    assert a[0][6]["iterations"] >= 3 and a[0][0][1, 8] != 0.0
+    assert _bits(a[0][:6], b[0][:6]) and _log(a[0][6]) == _log(b[0][6]) and a[1] == b[1]
+
+
+# ---- 6. one camera's change drops one set -------------------------------------------------------------------------------------
+def test_a_change_drops_that_cameras_intrinsics_only():
+    k, pk, ok = mr.gpu_case("rf")
+    kr = dict(k, kinds="RR")
+    intr = np.array(k["intr0"], dtype=np.float64)
+    intr[:, 8] = 0.0123, 0.0456          # a k3 on both sets: camera 0 keeps its own, camera 1's slot 8 is not part of its model
+    prob = _create(kr)
+    _set_intrinsics(prob, kr, intr=intr)
+    prob.set_state(k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"])
+    poses = prob.get_state(want_cost=False)
+    prob.set_camera_model(1, capi.MODEL_FISHEYE)
+    with pytest.raises(capi.CcError, match="set_intrinsics") as e:
+        prob.solve(capi.default_options(**ok))
+    assert "cc error %d" % CC_ERR_STATE in str(e.value)
+    with pytest.raises(capi.CcError, match="set_intrinsics"):
+        prob.eval()
+    with pytest.raises(capi.CcError, match="set_intrinsics"):
+        prob.estimate_start_pixels()
+    assert np.array_equal(prob.get_camera_intrinsics(0), intr[0])
+    assert _bits(poses[:4], prob.get_state(want_cost=False)[:4])
+    prob.set_camera_intrinsics(1, intr[1], 0)
+    assert prob.get_camera_intrinsics(1)[8] == 0.0 and prob.get_camera_intrinsics(0)[8] == intr[0, 8]
+    s = prob.solve(capi.default_options(**ok))
+    assert s["iterations"] >= 3 and prob.get_camera_intrinsics(1)[8] == 0.0 and prob.get_camera_intrinsics(0)[8] != 0.0
+    # set_intrinsics (every set at once) applies the slot rule set by set
+    prob.set_intrinsics(intr[0], 0)
+    got = prob.get_camera_intrinsics()
+    prob.close()
+    assert got[0, 8] == intr[0, 8] and got[1, 8] == 0.0 and np.array_equal(got[1, :8], intr[0, :8])
+
+
+# ---- 7. refusals --------------------------------------------------------------------------------------------------------------
+def _refused(call, code, *needles):
+    with pytest.raises(capi.CcError) as e:
+        call()
+    assert "cc error %d:" % code in str(e.value) and len(str(e.value)) > 20 and all(n in str(e.value) for n in needles), str(e.value)
+
+
+def test_refusals_leave_the_handle_as_it_was():
+    k, pk, ok = mr.gpu_case("rf")
+    ref_cost = None
+    # a shared-set handle and a poses-only handle
+    shared = _create(k, kind=True)
+    _refused(lambda: shared.set_camera_model(1, capi.MODEL_FISHEYE), CC_ERR_STATE, "cc_rigk_set_model")
+    _refused(lambda: shared.get_camera_model(0), CC_ERR_STATE)
+    assert shared.get_model() == capi.MODEL_RADTAN
+    shared.close()
+    plain = _create(k, kind=False)
+    _refused(lambda: plain.set_camera_model(1, capi.MODEL_FISHEYE), CC_ERR_STATE, "without intrinsics")
+    _refused(lambda: plain.get_camera_model(0), CC_ERR_STATE, "without intrinsics")
+    plain.close()
+    # bad arguments on a mixed handle with everything set: the models, the intrinsics and the evaluation stay
+    prob = _problem(k, **pk)
+    ref_cost = prob.eval()
+    intr = prob.get_camera_intrinsics()
+    for cam, model in ((-1, capi.MODEL_FISHEYE), (2, capi.MODEL_RADTAN), (0, 7), (0, capi.MODEL_MIXED), (1, capi.MODEL_MIXED)):
+        _refused(lambda: prob.set_camera_model(cam, model), CC_ERR_BAD_ARGUMENT)
+    _refused(lambda: prob.get_camera_model(-1), CC_ERR_BAD_ARGUMENT)
+    _refused(lambda: prob.get_camera_model(2), CC_ERR_BAD_ARGUMENT)
+    assert capi.lib().cc_rigk_get_camera_model(prob._h, C.c_int64(0), None) == CC_ERR_BAD_ARGUMENT
+    _refused(lambda: prob.set_model(capi.MODEL_MIXED), CC_ERR_BAD_ARGUMENT, "unknown model")
+    _refused(prob.exchange_export, CC_ERR_STATE, "fisheye model")
+    _refused(lambda: prob.comm_init(bytes(128), 0, 1), CC_ERR_STATE, "fisheye model")
+    _refused(lambda: prob.exchange_attach(0, [bytes(64)]), CC_ERR_STATE, "fisheye model")
+    assert prob.get_model() == capi.MODEL_MIXED and prob.get_camera_model() == [capi.MODEL_RADTAN, capi.MODEL_FISHEYE]
+    assert prob.get_camera_model(1) == capi.MODEL_FISHEYE
+    assert np.array_equal(prob.get_camera_intrinsics(), intr) and prob.eval() == ref_cost
+    prob.set_camera_model(1, capi.MODEL_FISHEYE)          # the model it has: a no-op, the intrinsics stay
+    assert prob.eval() == ref_cost
+    # set_model keeps its meaning: every camera gets the model, all intrinsics go
+    prob.set_model(capi.MODEL_RADTAN)
+    assert prob.get_model() == capi.MODEL_RADTAN and prob.get_camera_model() == [capi.MODEL_RADTAN, capi.MODEL_RADTAN]
+    _refused(prob.eval, CC_ERR_STATE, "set_intrinsics")
+    prob.close()
+    # a handle with an exchange refuses a fisheye camera
+    ex = _create(k)
+    ex.exchange_export()
+    _refused(lambda: ex.set_camera_model(1, capi.MODEL_FISHEYE), CC_ERR_STATE, "exchange or a communicator")
+    ex.set_camera_model(1, capi.MODEL_RADTAN)
+    assert ex.get_camera_model() == [capi.MODEL_RADTAN, capi.MODEL_RADTAN]
+    ex.close()
+
+
+# ---- 8. the pixel start -------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _start_reference(name):
+    """The reference's solve from the SCENARIO's start at the tight tolerances, and the 50-digit inverse of every pixel under its
+    own camera's model at the start intrinsics, rounded to float32."""
+    k, pk, _ = mr.gpu_case(name)
+    want = mr.solve_case(k, mr.problem(k, **pk), options=tight_options())
+    pts = np.full((len(k["obs_cam"]), 2), np.nan, dtype=np.float32)
+    for c, m in enumerate(mr.model_ids(k["kinds"])):
+        sel = np.asarray(k["obs_cam"]) == c
+        pts[sel] = sref.unproject(m, k["intr0"][c], k["obs_uv_pix"][sel]).astype(np.float32)
+    return want, pts
+
+
+@pytest.mark.parametrize("name", ["rf", "percam_start"])
+def test_pixel_start_uses_each_cameras_own_model(name):
+    """From identity poses: start_points is the float32 rounding of the 50-digit inverse of each camera's own model at the start
+    intrinsics -- no point differs, none is NaN -- and start + solve ends at the reference's minimum from the scenario's start,
+    to the bounds of tests/test_gpu_rigk_start.py (tests/test_rigk_start_ref_cpu.py derives them). percam_start is percam's rig
+    and loss, undisplaced, without percam's masks: with them the reference's own solves from the two starts end 7.1e-10 rad apart,
+    beyond the 5.78e-10 of the bound (tests/rigk_mixed_ref.py; the GPU, measured with masks and loss: 7.30e-10, the reference's
+    figure to three digits)."""
+    k, pk, _ = mr.gpu_case(name)
+    want, want_pts = _start_reference(name)
+    prob = _problem(k, state=False, **pk)
+    rep = prob.estimate_start_pixels()
+    got_pts, bad = prob.start_points()
+    n_diff = int((got_pts != want_pts).sum())
+    print("%s: %d points, %d coordinates differ from the reference's rounding, %d NaN" % (name, len(got_pts), n_diff, bad))
+    assert rep["views_invalid"] == 0 and rep["cameras_unplaced"] == 0 and rep["frames_unplaced"] == 0
+    summary = prob.solve(capi.default_options(**TIGHT))
+    got = (prob.get_camera_intrinsics(),) + prob.get_state(want_cost=True) + (summary,)
+    prob.close()
+    d = distances(want, got)
+    print(f"{name}: reference {want[6]['final_cost']:.9e} ({want[6]['iterations']} it) vs start + solve {summary['final_cost']:.9e} "
+          f"({summary['iterations']} it): cost rel {d[0]:.2e} ({d[0] / COST_REL:.3f} of bound), cam_R {d[1]:.2e} ({d[1] / CAM_R_ABS:.3f}), "
+          f"cam_t {d[2]:.2e} ({d[2] / CAM_T_ABS:.3f}), intrinsics {d[3]:.2e} ({d[3] / INTR_REL:.3f})")
+    assert bad == 0 and n_diff == 0
+    assert d[0] <= COST_REL and d[1] <= CAM_R_ABS and d[2] <= CAM_T_ABS and d[3] <= INTR_REL
+
+
+# ---- 9. the one-shot call -----------------------------------------------------------------------------------------------------
+def test_rigk_estimate_with_a_model_per_camera_is_the_stepwise_sequence():
+    k, pk, ok = mr.gpu_case("rf")
+    models = mr.model_ids(k["kinds"])
+    prob = _problem(k, state=False, **pk)
+    rep = prob.estimate_start_pixels()
+    s = prob.solve(capi.default_options(**ok))
+    step = (prob.get_camera_intrinsics(),) + prob.get_state()
+    prob.close()
+    args = (k["cams"], k["frame_offsets"], k["obs_cam"], k["obs_world"], k["obs_uv_pix"], k["world_xyz"], k["cam_frozen"], k["intr0"])
+    one = capi.rigk_estimate(*args, model=models, per_camera=True, options=capi.default_options(**ok))
+    assert _bits(one[:6], step) and _log(one[6]) == _log(s) and one[6]["iterations"] == s["iterations"] >= 3
+    assert {a: (b.tolist() if a == "parent" else b) for a, b in one[7].items()} == {a: (b.tolist() if a == "parent" else b) for a, b in rep.items()}
+    with pytest.raises(ValueError):
+        capi.rigk_estimate(*args[:7], k["intr0"][0], model=models, per_camera=False)
+    with pytest.raises(ValueError):
+        capi.rigk_estimate(*args, model=models + [0], per_camera=True)
+
+
+def test_profiled_rounds_count_a_launch_per_model():
+    """Under profile_kernels both launches of a sweep count as CC_K_SWEEP: two per sweep in kernel_launches."""
+    k, pk, ok = mr.gpu_case("rf")
+    prob = _problem(k, **pk)
+    s = prob.solve(capi.default_options(profile_kernels=1, **ok))
+    prob.close()
+    assert s["iterations"] == mr.gpu_reference("rf")[6]["iterations"]
+    assert s["kernel_ms"]["sweep"] > 0.0 and s["kernel_launches"]["sweep"] >= 2 * s["iterations"]
