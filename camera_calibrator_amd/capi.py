@@ -85,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "cc_rig_create", "cc_rig_destroy", "cc_rig_set_state", "cc_rig_reset", "cc_rig_solve",
     "cc_rig_get_state", "cc_rig_solver_form", "cc_rig_solver_status", "cc_rig_eval", "cc_rig_optimize", "cc_rig_comm_init", "cc_rig_exchange_export", "cc_rig_exchange_attach", "cc_rigk_create",
     "cc_rigk_set_intrinsics", "cc_rigk_get_intrinsics", "cc_rigk_create_per_camera", "cc_rigk_set_camera_intrinsics",
-    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_rigk_set_camera_model", "cc_rigk_get_camera_model", "cc_rigk_estimate_start", "cc_rigk_start_points", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
+    "cc_rigk_get_camera_intrinsics", "cc_rigk_set_model", "cc_rigk_get_model", "cc_rigk_set_camera_model", "cc_rigk_get_camera_model", "cc_rigk_estimate_start", "cc_rigk_start_points", "cc_rigk_estimate_start_bearing", "cc_rigk_start_bearings", "cc_zhang_init", "cc_intrinsics_optimize_multi", "cc_rig_optimize_multi", "cc_rig_optimize_frames", "cc_rig_optimize_columns",
     "cc_rig_set_inner_iterations", "cc_rig_inner_pass", "cc_rig_inner_status",
     "cc_rig_start_options_init", "cc_rig_estimate_start", "cc_rig_start_views", "cc_rig_estimate",
     "cc_intrinsics_batch_create", "cc_intrinsics_batch_destroy", "cc_intrinsics_batch_set_state", "cc_intrinsics_batch_get_state",
@@ -881,6 +881,11 @@ class RigProblem:
         invalid. Same arguments and report; the intrinsics are not written."""
         return self._estimate_start(lib().cc_rigk_estimate_start, cam_q, cam_t, frame_q, frame_t, refine_iterations)
 
+    def estimate_start_bearings(self, cam_q=None, cam_t=None, frame_q=None, frame_t=None, refine_iterations=10):
+        """estimate_start_pixels on unit bearings instead of x / z (cc_rigk_estimate_start_bearing): for rigs whose points reach
+        or pass 90 degrees off the optical axis. Same arguments and report; the intrinsics are not written."""
+        return self._estimate_start(lib().cc_rigk_estimate_start_bearing, cam_q, cam_t, frame_q, frame_t, refine_iterations)
+
     def _estimate_start(self, call, cam_q, cam_t, frame_q, frame_t, refine_iterations):
         opt = RigStartOptions(refine_iterations=int(refine_iterations))
         rep = RigStartReport()
@@ -917,6 +922,14 @@ class RigProblem:
         bad = C.c_int64(0)
         _check(lib().cc_rigk_start_points(self._h, _p(uv, C.c_float), C.byref(bad)))
         return uv, int(bad.value)
+
+    def start_bearings(self):
+        """(b [n_obs, 3] float32, n_without_root): the unit bearings the last estimate_start_bearings used, in the caller's
+        observation order (NaN x 3: no root), and how many of them are NaN (cc_rigk_start_bearings)."""
+        b = np.zeros((self.n_obs, 3), dtype=np.float32)
+        bad = C.c_int64(0)
+        _check(lib().cc_rigk_start_bearings(self._h, _p(b, C.c_float), C.byref(bad)))
+        return b, int(bad.value)
 
     def comm_init(self, unique_id, rank, nranks):
         buf = (C.c_uint8 * 128).from_buffer_copy(bytes(unique_id))
@@ -1001,12 +1014,15 @@ def rig_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, c
 
 def rigk_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, world_xyz, cam_frozen, intr, const_mask=0, model=MODEL_RADTAN,
                   per_camera=False, cam_q=None, cam_t=None, frame_q=None, frame_t=None, huber_a=0.0, options=None, device=0,
-                  log_capacity=2048):
+                  log_capacity=2048, start="pinhole"):
     """Start, then solve, for the rig problem with intrinsics: a with_intrinsics handle (per_camera: one set per camera), its
     model (one, or with per_camera a sequence of n_cams: set_camera_model, applied before the intrinsics), intr ([9], or
     [n_cams, 9] per camera) and const_mask (one, or one per camera) as the start intrinsics,
-    estimate_start_pixels with the pose arrays as the caller's poses (None: the identity), solve. Returns
+    estimate_start_pixels (start="pinhole") or estimate_start_bearings (start="bearing": points at or beyond 90 degrees off the
+    axis) with the pose arrays as the caller's poses (None: the identity), solve. Returns
     (intr, cam_q, cam_t, frame_q, frame_t, obs_cost, summary, report); intr is [9], or [n_cams, 9] per camera."""
+    if start not in ("pinhole", "bearing"):
+        raise ValueError("rigk_estimate: start must be 'pinhole' or 'bearing', not %r" % (start,))
     models = None
     if not np.isscalar(model):
         models = [int(m) for m in model]
@@ -1029,7 +1045,7 @@ def rigk_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv_pixels, worl
                 p.set_camera_intrinsics(c, intr[c], int(masks[c]))
         else:
             p.set_intrinsics(intr, int(const_mask))
-        report = p.estimate_start_pixels(cam_q, cam_t, frame_q, frame_t)
+        report = (p.estimate_start_bearings if start == "bearing" else p.estimate_start_pixels)(cam_q, cam_t, frame_q, frame_t)
         summary = p.solve(options, log_capacity=log_capacity)
         out = p.get_camera_intrinsics() if per_camera else p.get_intrinsics()
         return (out,) + p.get_state() + (summary, report)

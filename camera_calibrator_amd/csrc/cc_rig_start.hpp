@@ -40,6 +40,12 @@ struct RigStartDev {
 };
 
 void rig_start_enqueue_views(const RigStartDev& P, hipStream_t s, int refine_iterations);
+// EXTENSION: stages V and R on float3 unit bearings [3N] in the order of the observations (cc_rigk_estimate_start_bearing;
+// cc_rigk_start.hpp makes them). k_rig_start_view_bearing is k_rig_start_view restated: the closed form from b x (P y~) = 0, the
+// refinement on the chord p / |p| - b, rms^2 = cost / (2 n); the record is the same, P.uv is not read. The bearings are an
+// argument of their own: RigStartDev, and with it the other kernels' arguments, stays as it is. The kernel is a translation
+// unit of its own (cc_rig_start_bearing.hip, text in cc_rig_start_bearing_dev.hpp).
+void rig_start_enqueue_views_bearing(const RigStartDev& P, const float* bearing, hipStream_t s, int refine_iterations);
 void rig_start_enqueue_poses(const RigStartDev& P, hipStream_t s, int n_edges);
 
 }  // namespace cc

@@ -143,4 +143,83 @@ __global__ __launch_bounds__(64) void k_rigk_start_unproject(RigkStartDev P) {
   }
 }
 
+// ---- the bearing start: unit directions instead of x / z ------------------------------------------------------------------------
+// rigk_fisheye_root with the interval [0, pi): the same rule, the bracket's far end at the double below pi. A point at 90 degrees
+// off the axis and beyond it has a theta like any other; only tan(theta) had none.
+__device__ __forceinline__ bool rigk_fisheye_root_pi(const double* __restrict__ k, double td, double* theta) {
+  const double top = 3.141592653589793;   // the double below pi
+  const bool bracketed = rigk_fisheye_theta_d(k, top) - td > 0.0;
+  double lo = 0.0, hi = top;
+  double th = td < top ? td : 0.5 * top;
+  bool found = false;
+  for (int it = 0; it < 200; ++it) {
+    const double f = rigk_fisheye_theta_d(k, th) - td;
+    const double fp = rigk_fisheye_slope(k, th);
+    if (f == 0.0) { found = true; break; }
+    double tn = th - f / fp;
+    if (bracketed) {
+      if (f > 0.0) hi = th; else lo = th;
+      if (!(fp > 0.0) || !(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
+    } else if (!(fp > 0.0) || !(tn >= 0.0 && tn <= top)) {
+      break;
+    }
+    const bool small = fabs(tn - th) <= 4.5e-16 * th;
+    th = tn;
+    if (small) { found = true; break; }
+  }
+  *theta = th;
+  return found || bracketed;
+}
+
+// One view's pixels into float3 unit bearings (three floats per observation, packed); NaN x 3: no bearing.
+__device__ __forceinline__ void rigk_bearing_view(const RigkBearingDev& P, int64_t g, bool fish, const double* __restrict__ k) {
+  const int64_t s0 = P.goff[g], s1 = P.goff[g + 1];
+  const double fx = k[0], fy = k[1], px = k[2], py = k[3];
+  const bool focal_ok = isfinite(fx) && isfinite(fy) && fx != 0.0 && fy != 0.0;
+  const float2* __restrict__ uv2 = reinterpret_cast<const float2*>(P.uv);
+  float* __restrict__ out = P.out;
+  const float nanf_ = __builtin_nanf("");
+  for (int64_t i = s0 + threadIdx.x; i < s1; i += 64) {
+    const float2 p = uv2[i];
+    float o0 = nanf_, o1 = nanf_, o2 = nanf_;
+    if (focal_ok && isfinite(p.x) && isfinite(p.y)) {
+      const double xd = ((double)p.x - px) / fx, yd = ((double)p.y - py) / fy;
+      if (fish) {
+        const double td = sqrt(xd * xd + yd * yd);
+        double th;
+        if (td == 0.0) { o0 = 0.0f; o1 = 0.0f; o2 = 1.0f; }   // the axis itself
+        else if (td > 0.0 && rigk_fisheye_root_pi(k, td, &th)) {
+          const double s = sin(th) / td;
+          o0 = (float)(xd * s); o1 = (float)(yd * s); o2 = (float)cos(th);
+        }
+      } else {
+        double x, y;
+        if (rigk_radtan_root(k, xd, yd, &x, &y)) {
+          const double s = 1.0 / sqrt(x * x + y * y + 1.0);
+          o0 = (float)(x * s); o1 = (float)(y * s); o2 = (float)s;
+        }
+      }
+    }
+    if (isnan(o0) || isnan(o1) || isnan(o2)) { o0 = nanf_; o1 = nanf_; o2 = nanf_; }   // (all three components or none)
+    out[i * 3] = o0; out[i * 3 + 1] = o1; out[i * 3 + 2] = o2;
+  }
+}
+
+// one wave per view, one model for the handle (P.cmodel is not read)
+__global__ __launch_bounds__(64) void k_rigk_start_bearing(RigkBearingDev P) {
+  const int64_t g = blockIdx.x;
+  if (g >= P.NG) return;
+  const double* __restrict__ k = P.intr + (size_t)P.kset[P.gcam[g]] * 16;   // (the same for every lane: scalar loads)
+  rigk_bearing_view(P, g, P.model == CC_MODEL_FISHEYE, k);
+}
+
+// ... with the model of the view's camera (CC_MODEL_MIXED)
+__global__ __launch_bounds__(64) void k_rigk_start_bearing_cam(RigkBearingDev P) {
+  const int64_t g = blockIdx.x;
+  if (g >= P.NG) return;
+  const int cam = P.gcam[g];
+  const double* __restrict__ k = P.intr + (size_t)P.kset[cam] * 16;
+  rigk_bearing_view(P, g, P.cmodel[cam] == CC_MODEL_FISHEYE, k);
+}
+
 }  // namespace cc

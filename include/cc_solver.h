@@ -578,7 +578,8 @@ int cc_rigk_get_camera_model(cc_rig* h, int64_t camera, int32_t* model);
  * A pixel without a point (no root, a non-finite pixel, a zero or non-finite fx / fy) becomes NaN, NaN and makes its view
  * INVALID, as a non-finite coordinate does in cc_rig_estimate_start: single observations are not dropped. Intrinsics under which
  * no view is valid are not an error: CC_OK, every pose keeps the caller's value, the report counts the views as invalid.
- * The pinhole form x / z of the normalised point limits the start to points well inside 90 degrees off the axis (README).
+ * The pinhole form x / z of the normalised point limits THIS start to points well inside 90 degrees off the axis; wider rigs
+ * start from cc_rigk_estimate_start_bearing below.
  * cc_rigk_start_points: the normalised points of the last cc_rigk_estimate_start in the CALLER's observation order (2 floats
  * per observation) and how many of them are NaN; either output may be NULL.
  * CC_ERR_STATE, the handle unchanged: a poses-only handle (cc_rig_create: use cc_rig_estimate_start), no intrinsics set (never,
@@ -587,6 +588,33 @@ int cc_rigk_get_camera_model(cc_rig* h, int64_t camera, int32_t* model);
 int cc_rigk_estimate_start(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t,
                            const double* frame_q, const double* frame_t, cc_rig_start_report* report);
 int cc_rigk_start_points(cc_rig* h, float* uv_normalised, int64_t* n_without_root);
+/* EXTENSION: cc_rigk_estimate_start on UNIT BEARINGS instead of x / z, for rigs whose points reach or pass 90 degrees off the
+ * optical axis (surround-view fisheye lenses of 185 - 200 degrees), where a normalised image point does not exist. Arguments,
+ * options, report, the meaning of the caller's poses and the CC_ERR_STATE cases are those of cc_rigk_estimate_start; the handle
+ * may have one shared set, a set per camera or a model per camera. The result becomes the handle's state (cc_rig_reset returns
+ * to it), intrinsics, masks and models are not written, cc_rig_start_views reads the views back. cc_rigk_estimate_start keeps
+ * its arithmetic and its bits; this is a second entry point, not its replacement.
+ *   bearing of a pixel (device, double precision on the float pixel, rounded to three floats):
+ *     radial-tangential: the root (x, y) exactly as in cc_rigk_estimate_start, b = (x, y, 1) / |(x, y, 1)|
+ *     fisheye: theta in [0, pi) -- not [0, pi/2) -- with theta_d(theta) = |distorted point| by the same rule (Newton steps that
+ *       fall back to bisection inside the bracket 0 .. the double below pi; plain Newton up the first rising branch when the far
+ *       end does not bracket), b = (sin theta (xd, yd) / theta_d, cos theta); the axis gives exactly (0, 0, 1)
+ *     no root, a non-finite pixel, a zero or non-finite fx / fy: NaN x 3, the view INVALID (single observations are not dropped)
+ *   stage V: the same classification, centring, scaling and board basis; P (3 x 3 on a board's coordinates, 3 x 4 otherwise) is
+ *     the null vector of the Gram sum_i (I - b_i b_i^T) (x) y~_i y~_i^T, which is b x (P y~) = 0. General views keep
+ *     P / cbrt(det P_3x3); planar views scale by 1 / |first column| and take the sign with sum_i b_i . (P y~_i) > 0, the points
+ *     along their bearings (t_z > 0 would be wrong for a board that the camera's plane cuts)
+ *   stage R: Levenberg-Marquardt on the chord r = p / |p| - b, p = R X + t, the same updates and damping, a step accepted when
+ *     the cost drops and is finite (no depth test: nothing is singular short of p = 0); rms^2 = cost / (2 n), a squared angle
+ *     for small errors -- the unit of the x / z form near the axis, so the weights of stages C and F keep their meaning
+ * (a bearing is normalised again in double precision where it is used: the rounding to float leaves its length 6e-8 off 1).
+ * cc_rigk_start_bearings: the bearings of the last cc_rigk_estimate_start_bearing in the CALLER's observation order (3 floats per
+ * observation) and how many are NaN; either output may be NULL. CC_ERR_STATE before a bearing start has run and after a
+ * cc_rigk_estimate_start since; cc_rigk_start_points likewise returns CC_ERR_STATE after a bearing start: each reads its own
+ * start's buffer only. */
+int cc_rigk_estimate_start_bearing(cc_rig* h, const cc_rig_start_options* opt, const double* cam_q, const double* cam_t,
+                                   const double* frame_q, const double* frame_t, cc_rig_start_report* report);
+int cc_rigk_start_bearings(cc_rig* h, float* bearing_xyz, int64_t* n_without_root);
 
 /* One-shot: the call ExtrinsicsCalibrator::Optimize makes in place of
  * extrinsics_calibrator.cpp:92-225. opt == NULL -> cc_options_init with max_iterations = 1000. */
