@@ -13,10 +13,10 @@
 //   k_rig_persist_w    the whole solve in one launch for rigs of at most four observed cameras (lean persistent form)
 //   k_rig_sweep_k2     extension (intrinsics): 16-column Gram on plain FMAs, two waves per group, compact records
 //   k_rig_sweep_adjk   extension, tiles (large rigs; CC_RIG_K_COMPACT=0)
-//   k_rig_sweep_adjk_fisheye   extension, tiles, the fisheye pixel model (cc_rigk_set_model; a unit of its own: cc_rig_fisheye.hip)
-//   k_rig_sweep_adjk_sel       extension, tiles, a pixel model per camera (cc_rigk_set_camera_model; cc_rig_mixed.hip): ONE LAUNCH PER
-//                              MODEL that has a group, so under profile_kernels a sweep of a mixed handle counts two launches of
-//                              CC_K_SWEEP in kernel_launches while `sweeps` of the summary stays one per round
+//   k_rig_sweep_lens   extension, tiles, a unit of its own (cc_rig_lens.hip): the fisheye pixel model (cc_rigk_set_model), or a pixel
+//                      model per camera (cc_rigk_set_camera_model) with ONE LAUNCH PER MODEL that has a group, so under
+//                      profile_kernels a sweep of a mixed handle counts two launches of CC_K_SWEEP in kernel_launches while
+//                      `sweeps` of the summary stays one per round
 // (The first formulation -- every row's 13 / 22 columns through the matrix pipe, k_rig_sweep -- lost to the adjoint forms in
 // round 2 and was deleted in round 5; git history has it.) Only cameras that are
 // observed AND not frozen own columns of the reduced system (any number of frozen / unobserved cameras
@@ -50,8 +50,8 @@
 #include "cc_persist_dev.hpp"
 #include "cc_rig_dev.hpp"
 #include "cc_rig_inner.hpp"
-#include "cc_rig_fisheye.hpp"
-#include "cc_rig_mixed.hpp"
+#include "cc_rig_lens.hpp"
+#include "cc_rig_lens_dev.hpp"
 #include "cc_rig_start.hpp"
 #include "cc_rigk_start.hpp"
 #include "cc_rig_tree.hpp"
@@ -230,29 +230,9 @@ __device__ __forceinline__ void rig_common(const double* Rf, const double* tf, c
 // EXTENSION: pixel model behind the rig chain. Given the normalised point (o.x, o.y, o.iz) it returns
 // the pixel residuals, B = d residual / d x_cam (what rig_row chains through both poses) and the two
 // rows of d residual / d k (DistortNormalized / DistortPixels, calibrator.cpp:70-95).
-struct RigKObs {
-  double ru, rv, Bu0, Bu1, Bu2, Bv0, Bv1, Bv2;
-  double ju[9], jv[9];
-};
+using RigKObs = LensRadtanRows;   // (cc_rig_lens_dev.hpp: the arithmetic, shared with the kernels of cc_rig_lens.hip)
 __device__ __forceinline__ void rigk_obs(const double* k, const RigObs& o, double u, double v, RigKObs& r) {
-  const double x = o.x, y = o.y, iz = o.iz;
-  const double fx = k[0], fy = k[1];
-  const double r2 = x * x + y * y, r4 = r2 * r2, r6 = r4 * r2;
-  const double m = 1.0 + k[4] * r2 + k[5] * r4 + k[8] * r6;
-  const double xd = x * m + 2.0 * k[6] * x * y + k[7] * (r2 + 2.0 * x * x);
-  const double yd = y * m + 2.0 * k[7] * x * y + k[6] * (r2 + 2.0 * y * y);
-  r.ru = fx * xd + k[2] - u;
-  r.rv = fy * yd + k[3] - v;
-  r.ju[0] = xd; r.ju[1] = 0.0; r.ju[2] = 1.0; r.ju[3] = 0.0;
-  r.ju[4] = fx * x * r2; r.ju[5] = fx * x * r4; r.ju[6] = fx * 2.0 * x * y; r.ju[7] = fx * (r2 + 2.0 * x * x); r.ju[8] = fx * x * r6;
-  r.jv[0] = 0.0; r.jv[1] = yd; r.jv[2] = 0.0; r.jv[3] = 1.0;
-  r.jv[4] = fy * y * r2; r.jv[5] = fy * y * r4; r.jv[6] = fy * (r2 + 2.0 * y * y); r.jv[7] = fy * 2.0 * x * y; r.jv[8] = fy * y * r6;
-  const double mp = k[4] + 2.0 * k[5] * r2 + 3.0 * k[8] * r4;
-  const double dxx = m + 2.0 * mp * x * x + 2.0 * k[6] * y + 6.0 * k[7] * x;
-  const double dxy = 2.0 * mp * x * y + 2.0 * k[6] * x + 2.0 * k[7] * y;
-  const double dyy = m + 2.0 * mp * y * y + 2.0 * k[7] * x + 6.0 * k[6] * y;
-  r.Bu0 = fx * dxx * iz; r.Bu1 = fx * dxy * iz; r.Bu2 = -(fx * dxx * x + fx * dxy * y) * iz;
-  r.Bv0 = fy * dxy * iz; r.Bv1 = fy * dyy * iz; r.Bv2 = -(fy * dxy * x + fy * dyy * y) * iz;
+  lens_radtan_rows(k, o.x, o.y, o.iz, u, v, r);
 }
 
 #include "cc_rig_sweeps.hpp"
@@ -319,8 +299,8 @@ struct cc_rig : cc::SolveHost {   // pinned: host_pub = h_ctl's block, [20] fail
   bool frame_allowed = true; // poses-only, three-kernel path: the FRAME form of the sweep (k_rig_sweep_frame); CC_RIG_SWEEP_FRAME=0: one workgroup per group (k_rig_sweep_adj)
   int frame_waves = 2;       // waves per frame workgroup of the frame form
   int kmode = 0;
-  int model = CC_MODEL_RADTAN;   // cc_rigk_set_model: the pixel model of every camera of the handle (fisheye: cc_rig_fisheye.hpp, tiles only);
-                                 // CC_MODEL_MIXED when the cameras differ (cc_rigk_set_camera_model: cc_rig_mixed.hpp, tiles only)
+  int model = CC_MODEL_RADTAN;   // cc_rigk_set_model: the pixel model of every camera of the handle (fisheye: cc_rig_lens.hpp, tiles only);
+                                 // CC_MODEL_MIXED when the cameras differ (cc_rigk_set_camera_model: cc_rig_lens.hpp, tiles only)
   std::vector<int32_t> cam_model;      // [C] the model of every camera (all equal to `model` unless that is CC_MODEL_MIXED)
   std::vector<uint8_t> intr_dropped;   // [C] a change of this camera's model dropped its intrinsics: set them before the next solve
   int32_t* d_cmodel = nullptr;         // [C] device copy of cam_model (a mixed handle; allocated by the first one)
@@ -639,7 +619,7 @@ static int rig_layout(cc_rig* h, const std::vector<uint8_t>& seen_any) {
     }
     if (int rc = dev_upload(h, &d.gk2, gk)) return rc;
   }
-  if (h->model == CC_MODEL_MIXED) {   // the cameras' models and one list of groups per model (cc_rig_mixed.hpp)
+  if (h->model == CC_MODEL_MIXED) {   // the cameras' models and one list of groups per model (cc_rig_lens.hpp)
     if (!h->d_cmodel) { if (int rc = dev_alloc(h, &h->d_cmodel, (size_t)C)) return rc; }
     if (!h->d_glist) { if (int rc = dev_alloc(h, &h->d_glist, (size_t)h->NG)) return rc; }
     std::vector<int32_t> gl;
@@ -825,13 +805,10 @@ static int rig_size_reduce_grid(cc_rig* h) {
   return 0;
 }
 
-static RigFishDev rig_fish_dev(const cc_rig* h) {
+static RigLensDev rig_lens_dev(const cc_rig* h) {
   const RigDev& d = h->d;
-  return RigFishDev{d.F, d.NG, d.C, d.CK, d.uv, d.oxyz, d.widx, d.wxyz, d.goff, d.gframe, d.gcam, d.cam_fixed, d.kset, d.kmask, d.cam, d.pose,
+  return RigLensDev{d.F, d.NG, d.C, d.CK, d.uv, d.oxyz, d.widx, d.wxyz, d.goff, d.gframe, d.gcam, d.cam_fixed, d.kset, d.kmask, d.cam, d.pose,
                     d.intr, d.camrec, d.frec, d.krec, d.gblocks, d.gstats, d.ghd0, d.ghdk, d.gcomp, d.ctl, d.gstride, d.huber_a, d.huber_b, d.huber_2a};
-}
-static RigMixedDev rig_mixed_dev(const cc_rig* h) {
-  return RigMixedDev{rig_fish_dev(h), h->d_cmodel, {h->d_glist, h->d_glist + h->nlist[0]}, {h->nlist[0], h->nlist[1]}};
 }
 static RigInnerDev rig_inner_dev(const cc_rig* h) {
   const RigDev& d = h->d;
@@ -851,7 +828,7 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
   const RigDev& d = h->d;
   struct RoundCount { cc_rig* h; ~RoundCount() { h->enq_round++; } } count_round{h};
   auto sweep = [&]() {
-    if (h->model == CC_MODEL_FISHEYE) rig_fisheye_enqueue_sweep(rig_fish_dev(h), h->stream, h->sweep_waves);
+    if (h->model == CC_MODEL_FISHEYE) rig_lens_enqueue_sweep(rig_lens_dev(h), h->stream, h->sweep_waves, CC_MODEL_FISHEYE, nullptr, (int)h->NG);
     else if (d.kcm) hipLaunchKernelGGL(k_rig_sweep_k2, dim3((unsigned)h->NG), dim3(128), 0, h->stream, d);   // (a workgroup of two waves per group)
     else if (d.kmode && h->sweep_waves == 1) hipLaunchKernelGGL(k_rig_sweep_adjk<1>, dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
     else if (d.kmode) hipLaunchKernelGGL(k_rig_sweep_adjk<4>, dim3((unsigned)h->NG), dim3(256), 0, h->stream, d);
@@ -872,9 +849,9 @@ static int rig_enqueue_round(cc_rig* h, bool initial, bool profile, bool publish
     else hipLaunchKernelGGL((k_rig_sweep_adj<1>), dim3((unsigned)h->NG), dim3(64), 0, h->stream, d);
   };
   if (h->model == CC_MODEL_MIXED) {   // one launch per model that has a group, one after the other; each a CC_K_SWEEP of its own when profiled
-    const RigMixedDev M = rig_mixed_dev(h);
+    const RigLensDev L = rig_lens_dev(h);   // (d_glist: the groups of model 0, then those of model 1)
     for (int m = 0; m < 2; ++m)
-      if (M.nlist[m] > 0) { Probe p(h, CC_K_SWEEP, profile); rig_mixed_enqueue_sweep(M, h->stream, h->sweep_waves, m); }
+      if (h->nlist[m] > 0) { Probe p(h, CC_K_SWEEP, profile); rig_lens_enqueue_sweep(L, h->stream, h->sweep_waves, m, h->d_glist + (m ? h->nlist[0] : 0), h->nlist[m]); }
   } else { Probe p(h, CC_K_SWEEP, profile); sweep(); }
   if (h->inner_on && !initial && !h->comm && !h->exchange) {
     // inner iterations (cc_rig_inner.hpp): a pass on the candidate, the sweep again at its result, the decision with the
@@ -1417,7 +1394,7 @@ int cc_rigk_get_model(cc_rig* h, int32_t* model) {
   return CC_OK;
 }
 
-// EXTENSION: the pixel model of ONE camera of a handle with a set of intrinsics per camera (cc_rig_mixed.hpp)
+// EXTENSION: the pixel model of ONE camera of a handle with a set of intrinsics per camera (cc_rig_lens.hpp)
 int cc_rigk_set_camera_model(cc_rig* h, int64_t camera, int32_t model) {
   using namespace cc;
   if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_rigk_set_camera_model: NULL handle");
@@ -1872,8 +1849,8 @@ int cc_rig_get_state(cc_rig* h, double* cam_q, double* cam_t, double* frame_q, d
     }
   }
   if (obs_cost && h->N > 0) {
-    if (h->model == CC_MODEL_FISHEYE) rig_fisheye_enqueue_obs_cost(rig_fish_dev(h), h->stream, cur, h->d_cost);
-    else if (h->model == CC_MODEL_MIXED) rig_mixed_enqueue_obs_cost(rig_mixed_dev(h), h->stream, cur, h->d_cost);
+    if (h->model != CC_MODEL_RADTAN)
+      rig_lens_enqueue_obs_cost(rig_lens_dev(h), h->stream, h->model == CC_MODEL_MIXED ? h->d_cmodel : nullptr, cur, h->d_cost);
     else hipLaunchKernelGGL(k_rig_obs_cost, dim3((unsigned)h->NG), dim3(256), 0, h->stream, h->d, cur, h->d_cost);
     CC_HIP(hipGetLastError());
     // through the cached pinned block (full PCIe rate, no fresh 8N-byte vector to fault in), back into the caller's order on

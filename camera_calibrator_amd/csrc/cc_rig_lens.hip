@@ -1,76 +1,35 @@
-// cc_rig_fisheye.hip -- kernels of the fisheye camera model on the rig problem with intrinsics (declarations and the outline:
-// cc_rig_fisheye.hpp). A translation unit of its own next to cc_rig.hip, whose kernel set is pinned (tests/test_kernel_budgets.py).
+// cc_rig_lens.hip -- kernels of the rig solve with intrinsics for the fisheye pixel model and for a pixel model per camera
+// (declarations and the outline: cc_rig_lens.hpp; the models' arithmetic: cc_rig_lens_dev.hpp). A translation unit of its own
+// next to cc_rig.hip, whose kernel set is pinned (tests/test_kernel_budgets.py).
 #include "cc_common.hpp"
 #include "cc_device.hpp"
-#include "cc_rig_fisheye.hpp"
+#include "cc_rig_dev.hpp"
+#include "cc_rig_lens.hpp"
+#include "cc_rig_lens_dev.hpp"
 
 namespace cc {
 
-// waves per SIMD the sweep is compiled for. k_rig_sweep_adjk fits the 168 registers of three; with the library atan2 and the ten
-// quantities of rig_fish_point alive across both rows the compiler wants 179 (one wave per group) / 189 (four), and at 168 it
-// spills 2 / 11 registers with reloads inside the pass loop. Two waves per SIMD: no spill, no scratch.
-constexpr int kRigFishWaves = 2;
-constexpr int kRigFishCompK = 320;  // doubles per group and buffer of the compact record: G (256), M (36) (kRigCompK, cc_rig_sweeps.hpp)
-
-// ceres::HuberLoss + Corrector: the arithmetic of huber_outlier / huber in cc_rig.hip, line for line (b = a^2 and a2 = 2 a come
-// from the caller: the same bits as the products formed here)
-__device__ __forceinline__ void rig_fish_huber(double a, double b, double a2, double s, double& rho, double& sr) {
-  if (s > b) {
-    const double y = rsqrt_pos(s);
-    const double r = s * y;
-    const double q = fmax(2.2250738585072014e-308, a * y);
-    sr = q * rsqrt_pos(q);
-    rho = a2 * r - b;
-  } else {
-    rho = s;
-    sr = 1.0;
-  }
-}
-
-// The model behind the pose chain: fisheye_common (cc_fisheye_dev.hpp) from the camera-frame point on, restated so that the
-// intrinsics kernels' translation units stay as they are. With w = theta^2, P = 1 + k1 w + .. + k4 w^4, Q = P + 2 w P',
-// g = (theta / rho) P, n^2 = rho^2 + zc^2, (cx, cy) = (xc, yc) / rho and D = Q zc / n^2 - g:
-//   xd = theta cx P,  d xd / d (xc, yc, zc) = (g + D cx^2, D cx cy, -Q xc / n^2),  d xd / d k_j = theta cx w^j   (yd alike).
-// D only ever meets cx^2, cx cy, cy^2 <= 1, so its rounding stays a few ulps of g for every rho > 0. On the axis itself
-// (rho = 0) the direction is taken as 0 and theta / rho as its limit 1 / zc.
-struct RigFishPoint {
-  double ex, ey, w, xd, yd, dxx, dxy, dyy, dxz, dyz;
-};
-__device__ __forceinline__ void rig_fish_point(const double* k, double xc, double yc, double zc, RigFishPoint& c) {
-  const double rho2 = xc * xc + yc * yc;
-  const double rho = sqrt(rho2);
-  const double th = atan2(rho, zc);
-  const bool off_axis = rho2 > 0.0;
-  const double ir = off_axis ? 1.0 / rho : 0.0;
-  const double cx = xc * ir, cy = yc * ir;
-  const double e = off_axis ? th * ir : 1.0 / zc;
-  c.w = th * th;
-  const double k1 = k[4], k2 = k[5], k3 = k[6], k4 = k[7];
-  const double P = 1.0 + c.w * (k1 + c.w * (k2 + c.w * (k3 + c.w * k4)));
-  const double Q = 1.0 + c.w * (3.0 * k1 + c.w * (5.0 * k2 + c.w * (7.0 * k3 + c.w * (9.0 * k4))));
-  const double g = e * P;
-  const double qz = Q / (rho2 + zc * zc);
-  const double D = qz * zc - g;
-  c.ex = th * cx;
-  c.ey = th * cy;
-  c.xd = c.ex * P;
-  c.yd = c.ey * P;
-  const double Dx = D * cx;
-  c.dxx = g + Dx * cx;
-  c.dxy = Dx * cy;
-  c.dyy = g + D * cy * cy;
-  c.dxz = -qz * xc;
-  c.dyz = -qz * yc;
-}
+// waves per SIMD the sweep is compiled for: three for the radial-tangential rows (<= 168 registers, as k_rig_sweep_adjk), two
+// for the fisheye rows. With the library atan2 and the ten quantities of lens_fish_point alive across both rows the compiler
+// wants 179 (one wave per group) / 189 (four) registers, and at 168 it spills 2 / 11 with reloads inside the pass loop; at two
+// waves per SIMD: no spill, no scratch. One kernel with a uniform branch on the model would put the
+// radial-tangential groups at two waves and carry the arctangent's live values through their pass loop.
+constexpr int kRigLensWavesRadtan = 3;
+constexpr int kRigLensWavesFisheye = 2;
+constexpr int kRigLensCompK = 320;  // doubles per group and buffer of the compact record: G (256), M (36) (kRigCompK, cc_rig_sweeps.hpp)
 
 // ---------------------------------------------------------------------------------------------
-// k_rig_sweep_adjk (cc_rig_sweeps.hpp) with the fisheye rows in place of rigk_obs. One workgroup of NW waves per (frame,
+// k_rig_sweep_adjk (cc_rig_sweeps.hpp) with the rows of MODEL in place of rigk_obs. One workgroup of NW waves per (frame,
 // camera) group: the 16 x 16 Gram G of X = [J_cam(6) r J_k(9)] on the matrix pipe, then the three tiles the other kernels
 // read, AA = N^T G[0:7, 0:7] N, AB = N^T G[0:7, 7:16], BB = G[7:16, 7:16] with N (7 x 13) = [I6 M 0; 0 0 1], and the compact
 // record (G, M) for the next sweep's model-cost term q = 1/2 (e'^T G e' - G[6][6]), e' = [dc + M_old df, 1, dk].
+// Workgroup b sweeps group g = b, or with LIST g = glist[b]: the groups of ONE model's cameras. Everything indexed by the group
+// -- the wave rotation, the compact record, the tiles, the statistics, the diagonals -- uses g. MODEL and LIST are compile-time
+// choices: each instantiation is the text of a kernel written out for it alone.
 // ---------------------------------------------------------------------------------------------
-template <int NW>
-__global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fisheye(RigFishDev P) {
+template <int NW, int MODEL, bool LIST>
+__global__ __launch_bounds__(NW * 64, MODEL == CC_MODEL_FISHEYE ? kRigLensWavesFisheye : kRigLensWavesRadtan)
+void k_rig_sweep_lens(RigLensDev P, const int32_t* __restrict__ glist /*not read without LIST*/) {
   constexpr int NT = NW * 64, EPT = 256 / NT;
   __shared__ __attribute__((aligned(16))) double s_stage[NW * kStageDoublesPerWave];   // per wave 64 x 16; then the partial products
   __shared__ double sm[96];        // camera record, frame record, intrinsics record (candidate [0..8], step [16..24])
@@ -80,7 +39,7 @@ __global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fishe
   __shared__ double s_m[36];       // M
   __shared__ double s_w[8];        // per wave: model-cost term, cost
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t g = blockIdx.x;
+  const int64_t g = LIST ? (int64_t)glist[blockIdx.x] : (int64_t)blockIdx.x;
   const int f = P.gframe[g], c = P.gcam[g];
   const int64_t s0 = P.goff[g], s1 = P.goff[g + 1];
   const LmCtl* ctl = P.ctl;
@@ -106,7 +65,7 @@ __global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fishe
   ObsRaw oa, ob;
   fetch(otid, oa);
   fetch(otid + NT, ob);
-  const double* comp_old = P.gcomp + ((size_t)cur * P.NG + g) * kRigFishCompK;
+  const double* comp_old = P.gcomp + ((size_t)cur * P.NG + g) * kRigLensCompK;
   {
     // records: camera [0..31], frame [32..63], intrinsics [64..95]; M of the accepted point
     const double r0 = tid < 32 ? P.camrec[c * 32 + tid] : (tid < 64 ? P.frec[(size_t)f * 32 + (tid - 32)] : P.krec[ks * 32 + ((tid - 64) & 31)]);
@@ -173,41 +132,69 @@ __global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fishe
     const double a0 = Rca[0] * r.X0 + Rca[1] * r.X1 + Rca[2] * r.X2 + tca[0];
     const double a1 = Rca[3] * r.X0 + Rca[4] * r.X1 + Rca[5] * r.X2 + tca[1];
     const double a2 = Rca[6] * r.X0 + Rca[7] * r.X1 + Rca[8] * r.X2 + tca[2];
-    RigFishPoint q;
-    rig_fish_point(kk, a0 + tcs[0], a1 + tcs[1], a2 + tcs[2], q);
-    const double fx = kk[0], fy = kk[1];
-    const double ru = fx * q.xd + kk[2] - r.u, rv = fy * q.yd + kk[3] - r.v;
-    double rho, sr;
-    rig_fish_huber(ha, hb, h2a, ru * ru + rv * rv, rho, sr);
-    if (valid) cost += 0.5 * rho;
-    if (!valid) sr = 0.0;
-    double w[16];
-    {   // u row: B_u = fx (dxx, dxy, dxz), J_k,u = [xd 0 1 0 | fx ex w, .. w^2, .. w^3, .. w^4 | 0]
-      const double b0 = fx * q.dxx, b1 = fx * q.dxy, b2 = fx * q.dxz;
-      w[0] = sr * (2.0 * (b2 * a1 - b1 * a2)); w[1] = sr * (2.0 * (b0 * a2 - b2 * a0)); w[2] = sr * (2.0 * (b1 * a0 - b0 * a1));
-      w[3] = sr * b0; w[4] = sr * b1; w[5] = sr * b2; w[6] = sr * ru;
-      const double j1 = fx * q.ex * q.w, j2 = j1 * q.w, j3 = j2 * q.w, j4 = j3 * q.w;
-      const double ju[9] = {q.xd, 0.0, 1.0, 0.0, j1, j2, j3, j4, 0.0};
+    if constexpr (MODEL == CC_MODEL_FISHEYE) {
+      LensFishPoint q;
+      lens_fish_point(kk, a0 + tcs[0], a1 + tcs[1], a2 + tcs[2], q);
+      const double fx = kk[0], fy = kk[1];
+      const double ru = fx * q.xd + kk[2] - r.u, rv = fy * q.yd + kk[3] - r.v;
+      double rho, sr;
+      lens_huber(ha, hb, h2a, ru * ru + rv * rv, rho, sr);
+      if (valid) cost += 0.5 * rho;
+      if (!valid) sr = 0.0;
+      double w[16];
+      {   // u row: B_u = fx (dxx, dxy, dxz), J_k,u = [xd 0 1 0 | fx ex w, .. w^2, .. w^3, .. w^4 | 0]
+        const double b0 = fx * q.dxx, b1 = fx * q.dxy, b2 = fx * q.dxz;
+        w[0] = sr * (2.0 * (b2 * a1 - b1 * a2)); w[1] = sr * (2.0 * (b0 * a2 - b2 * a0)); w[2] = sr * (2.0 * (b1 * a0 - b0 * a1));
+        w[3] = sr * b0; w[4] = sr * b1; w[5] = sr * b2; w[6] = sr * ru;
+        const double j1 = fx * q.ex * q.w, j2 = j1 * q.w, j3 = j2 * q.w, j4 = j3 * q.w;
+        const double ju[9] = {q.xd, 0.0, 1.0, 0.0, j1, j2, j3, j4, 0.0};
 #pragma unroll
-      for (int i = 0; i < 9; ++i) w[7 + i] = (kmask & (1u << i)) ? 0.0 : sr * ju[i];
-    }
-    stage_row(stage, lane, w);
-    wave_lds_fence();
-    gram_rows(stage, lane, acc0, acc1);
-    wave_lds_fence();
-    {   // v row: B_v = fy (dxy, dyy, dyz)
-      const double b0 = fy * q.dxy, b1 = fy * q.dyy, b2 = fy * q.dyz;
-      w[0] = sr * (2.0 * (b2 * a1 - b1 * a2)); w[1] = sr * (2.0 * (b0 * a2 - b2 * a0)); w[2] = sr * (2.0 * (b1 * a0 - b0 * a1));
-      w[3] = sr * b0; w[4] = sr * b1; w[5] = sr * b2; w[6] = sr * rv;
-      const double j1 = fy * q.ey * q.w, j2 = j1 * q.w, j3 = j2 * q.w, j4 = j3 * q.w;
-      const double jv[9] = {0.0, q.yd, 0.0, 1.0, j1, j2, j3, j4, 0.0};
+        for (int i = 0; i < 9; ++i) w[7 + i] = (kmask & (1u << i)) ? 0.0 : sr * ju[i];
+      }
+      stage_row(stage, lane, w);
+      wave_lds_fence();
+      gram_rows(stage, lane, acc0, acc1);
+      wave_lds_fence();
+      {   // v row: B_v = fy (dxy, dyy, dyz)
+        const double b0 = fy * q.dxy, b1 = fy * q.dyy, b2 = fy * q.dyz;
+        w[0] = sr * (2.0 * (b2 * a1 - b1 * a2)); w[1] = sr * (2.0 * (b0 * a2 - b2 * a0)); w[2] = sr * (2.0 * (b1 * a0 - b0 * a1));
+        w[3] = sr * b0; w[4] = sr * b1; w[5] = sr * b2; w[6] = sr * rv;
+        const double j1 = fy * q.ey * q.w, j2 = j1 * q.w, j3 = j2 * q.w, j4 = j3 * q.w;
+        const double jv[9] = {0.0, q.yd, 0.0, 1.0, j1, j2, j3, j4, 0.0};
 #pragma unroll
-      for (int i = 0; i < 9; ++i) w[7 + i] = (kmask & (1u << i)) ? 0.0 : sr * jv[i];
+        for (int i = 0; i < 9; ++i) w[7 + i] = (kmask & (1u << i)) ? 0.0 : sr * jv[i];
+      }
+      stage_row(stage, lane, w);
+      wave_lds_fence();
+      gram_rows(stage, lane, acc0, acc1);
+      wave_lds_fence();
+    } else {
+      const double iz = recip_depth(a2 + tcs[2]);
+      const double x = (a0 + tcs[0]) * iz, y = (a1 + tcs[1]) * iz;
+      LensRadtanRows ko;
+      lens_radtan_rows(kk, x, y, iz, r.u, r.v, ko);
+      double rho, sr;
+      lens_huber(ha, hb, h2a, ko.ru * ko.ru + ko.rv * ko.rv, rho, sr);
+      if (valid) cost += 0.5 * rho;
+      if (!valid) sr = 0.0;
+      double w[16];
+      w[0] = sr * (2.0 * (ko.Bu2 * a1 - ko.Bu1 * a2)); w[1] = sr * (2.0 * (ko.Bu0 * a2 - ko.Bu2 * a0)); w[2] = sr * (2.0 * (ko.Bu1 * a0 - ko.Bu0 * a1));
+      w[3] = sr * ko.Bu0; w[4] = sr * ko.Bu1; w[5] = sr * ko.Bu2; w[6] = sr * ko.ru;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) w[7 + q] = (kmask & (1u << q)) ? 0.0 : sr * ko.ju[q];
+      stage_row(stage, lane, w);
+      wave_lds_fence();
+      gram_rows(stage, lane, acc0, acc1);
+      wave_lds_fence();
+      w[0] = sr * (2.0 * (ko.Bv2 * a1 - ko.Bv1 * a2)); w[1] = sr * (2.0 * (ko.Bv0 * a2 - ko.Bv2 * a0)); w[2] = sr * (2.0 * (ko.Bv1 * a0 - ko.Bv0 * a1));
+      w[3] = sr * ko.Bv0; w[4] = sr * ko.Bv1; w[5] = sr * ko.Bv2; w[6] = sr * ko.rv;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) w[7 + q] = (kmask & (1u << q)) ? 0.0 : sr * ko.jv[q];
+      stage_row(stage, lane, w);
+      wave_lds_fence();
+      gram_rows(stage, lane, acc0, acc1);
+      wave_lds_fence();
     }
-    stage_row(stage, lane, w);
-    wave_lds_fence();
-    gram_rows(stage, lane, acc0, acc1);
-    wave_lds_fence();
   };
   // Observations are fetched TWO passes ahead (two register sets, the loop unrolled by two); each set is widened to doubles
   // BEFORE it is refilled, so the loaded registers are dead and the refill reuses them.
@@ -290,7 +277,7 @@ __global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fishe
         P.gstats[g * 2] = NW > 1 ? (s_w[4] + s_w[5]) + (s_w[6] + s_w[7]) : s_w[4];
         P.gstats[g * 2 + 1] = NW > 1 ? (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]) : s_w[0];
       }
-      if (lane < 36) P.gcomp[((size_t)dst * P.NG + g) * kRigFishCompK + 256 + lane] = s_m[lane];
+      if (lane < 36) P.gcomp[((size_t)dst * P.NG + g) * kRigLensCompK + 256 + lane] = s_m[lane];
     }
   };
   if (NW > 1) {
@@ -299,14 +286,18 @@ __global__ __launch_bounds__(NW * 64, kRigFishWaves) void k_rig_sweep_adjk_fishe
     role(0); role(1); role(2); role(3);
   }
 #pragma unroll
-  for (int e = 0; e < EPT; ++e) P.gcomp[((size_t)dst * P.NG + g) * kRigFishCompK + tid + e * NT] = s_G[tid + e * NT];
+  for (int e = 0; e < EPT; ++e) P.gcomp[((size_t)dst * P.NG + g) * kRigLensCompK + tid + e * NT] = s_G[tid + e * NT];
 }
 
-// per-observation robustified cost at the accepted point: k_rig_obs_cost (cc_rig.hip) for the fisheye residual -- the poses
-// from their quaternions, the camera-frame point by the two-step chain, no division by the depth
-__global__ void k_rig_obs_cost_fisheye(RigFishDev P, int cur, double* out /*sorted order*/) {
+// per-observation robustified cost at the accepted point: k_rig_obs_cost (cc_rig.hip) with the residual of the model of the
+// group's camera -- the poses from their quaternions, the camera-frame point by the two-step chain; the fisheye residual without
+// a division by the depth, the radial-tangential one on it, as k_rig_obs_cost forms it. cmodel == nullptr at compile time
+// (PER_CAMERA = false): every camera is fisheye
+template <bool PER_CAMERA>
+__device__ __forceinline__ void rig_lens_obs_cost(const RigLensDev& P, const int32_t* __restrict__ cmodel, int cur, double* out) {
   const int64_t g = blockIdx.x;
   const int f = P.gframe[g], c = P.gcam[g];
+  const bool fish = PER_CAMERA ? cmodel[c] == CC_MODEL_FISHEYE : true;
   const double* pc = P.cam + ((size_t)cur * P.C + c) * 8;
   const double* pf = P.pose + ((size_t)cur * P.F + f) * 8;
   double Rc[9], Rf[9];
@@ -324,22 +315,48 @@ __global__ void k_rig_obs_cost_fisheye(RigFishDev P, int cur, double* out /*sort
     const double xc = Rc[0] * r0 + Rc[1] * r1 + Rc[2] * r2 + pc[4];
     const double yc = Rc[3] * r0 + Rc[4] * r1 + Rc[5] * r2 + pc[5];
     const double zc = Rc[6] * r0 + Rc[7] * r1 + Rc[8] * r2 + pc[6];
-    RigFishPoint q;
-    rig_fish_point(kk, xc, yc, zc, q);
-    const double ru = kk[0] * q.xd + kk[2] - (double)m.x, rv = kk[1] * q.yd + kk[3] - (double)m.y;
+    double ru, rv;
+    if (fish) {
+      LensFishPoint q;
+      lens_fish_point(kk, xc, yc, zc, q);
+      ru = kk[0] * q.xd + kk[2] - (double)m.x;
+      rv = kk[1] * q.yd + kk[3] - (double)m.y;
+    } else {
+      const double iz = 1.0 / zc;
+      LensRadtanRows ko;
+      lens_radtan_rows(kk, xc * iz, yc * iz, iz, (double)m.x, (double)m.y, ko);
+      ru = ko.ru;
+      rv = ko.rv;
+    }
     double rho, sr;
-    rig_fish_huber(P.huber_a, P.huber_b, P.huber_2a, ru * ru + rv * rv, rho, sr);
+    lens_huber(P.huber_a, P.huber_b, P.huber_2a, ru * ru + rv * rv, rho, sr);
     out[idx] = 0.5 * rho;
   }
 }
-
-void rig_fisheye_enqueue_sweep(const RigFishDev& P, hipStream_t s, int waves) {
-  if (waves == 1) hipLaunchKernelGGL(k_rig_sweep_adjk_fisheye<1>, dim3((unsigned)P.NG), dim3(64), 0, s, P);
-  else hipLaunchKernelGGL(k_rig_sweep_adjk_fisheye<4>, dim3((unsigned)P.NG), dim3(256), 0, s, P);
+__global__ void k_rig_obs_cost_fisheye(RigLensDev P, int cur, double* out /*sorted order*/) { rig_lens_obs_cost<false>(P, nullptr, cur, out); }
+__global__ void k_rig_obs_cost_mixed(RigLensDev P, const int32_t* __restrict__ cmodel, int cur, double* out /*sorted order*/) {
+  rig_lens_obs_cost<true>(P, cmodel, cur, out);
 }
 
-void rig_fisheye_enqueue_obs_cost(const RigFishDev& P, hipStream_t s, int cur, double* out) {
-  hipLaunchKernelGGL(k_rig_obs_cost_fisheye, dim3((unsigned)P.NG), dim3(256), 0, s, P, cur, out);
+void rig_lens_enqueue_sweep(const RigLensDev& P, hipStream_t s, int waves, int model, const int32_t* glist, int n) {
+  if (n <= 0) return;
+  const dim3 grid((unsigned)n), block(waves == 1 ? 64 : 256);
+  if (!glist) {
+    if (waves == 1) hipLaunchKernelGGL((k_rig_sweep_lens<1, CC_MODEL_FISHEYE, false>), grid, block, 0, s, P, nullptr);
+    else hipLaunchKernelGGL((k_rig_sweep_lens<4, CC_MODEL_FISHEYE, false>), grid, block, 0, s, P, nullptr);
+  } else if (model == CC_MODEL_FISHEYE) {
+    if (waves == 1) hipLaunchKernelGGL((k_rig_sweep_lens<1, CC_MODEL_FISHEYE, true>), grid, block, 0, s, P, glist);
+    else hipLaunchKernelGGL((k_rig_sweep_lens<4, CC_MODEL_FISHEYE, true>), grid, block, 0, s, P, glist);
+  } else {
+    if (waves == 1) hipLaunchKernelGGL((k_rig_sweep_lens<1, CC_MODEL_RADTAN, true>), grid, block, 0, s, P, glist);
+    else hipLaunchKernelGGL((k_rig_sweep_lens<4, CC_MODEL_RADTAN, true>), grid, block, 0, s, P, glist);
+  }
+}
+
+void rig_lens_enqueue_obs_cost(const RigLensDev& P, hipStream_t s, const int32_t* cmodel, int cur, double* out) {
+  if (P.NG <= 0) return;
+  if (cmodel) hipLaunchKernelGGL(k_rig_obs_cost_mixed, dim3((unsigned)P.NG), dim3(256), 0, s, P, cmodel, cur, out);
+  else hipLaunchKernelGGL(k_rig_obs_cost_fisheye, dim3((unsigned)P.NG), dim3(256), 0, s, P, cur, out);
 }
 
 }  // namespace cc

@@ -7,8 +7,8 @@
 //                            handle's START intrinsics (what cc_rigk_set_intrinsics / _set_camera_intrinsics last wrote), into a
 //                            float2 normalised point; a pixel without a root gives NaN, NaN (the start then counts its view invalid)
 // RigStartDev::uv is pointed at the kernel's output and the start's kernels, tree and host code run on it as they are.
-// The kernel is a translation unit of its own (cc_rigk_start_dev.hpp has its text); cc_rig.hip launches it through the function
-// declared here.
+// The pixel start's kernels are a translation unit of their own (cc_rigk_start_dev.hpp has their text); cc_rig.hip launches them
+// through the functions declared here.
 
 namespace cc {
 
@@ -24,6 +24,19 @@ struct RigkStartDev {
 };
 
 void rigk_start_enqueue_unproject(const RigkStartDev& P, hipStream_t s);
+
+//   k_rigk_start_unproject_cam   the same with the model of each view's camera (CC_MODEL_MIXED)
+struct RigkStartCamDev {
+  int64_t NG;
+  const int32_t* cmodel;    // [C] CC_MODEL_RADTAN / CC_MODEL_FISHEYE of every camera
+  const float* uv;          // [N] float2 pixel observations, (frame, camera)-sorted
+  const int64_t* goff;      // [NG+1]
+  const int32_t* gcam;      // [NG]
+  const int32_t* kset;      // [C]
+  const double* intr;       // [sets][16] start intrinsics
+  float* out;               // [N] float2 normalised points, same order
+};
+void rigk_start_enqueue_unproject_cam(const RigkStartCamDev& P, hipStream_t s);
 
 // EXTENSION: the bearing form of the pixel start (cc_rigk_estimate_start_bearing), for points at and beyond 90 degrees off the
 // axis, where x / z does not exist:

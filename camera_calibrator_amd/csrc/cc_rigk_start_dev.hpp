@@ -1,5 +1,5 @@
-// cc_rigk_start_dev.hpp -- the kernel of the pixel start (cc_rigk_start.hpp says what it is for) and its device helpers, in a
-// header so that cc_rigk_start.hip is the launch only. All arithmetic is fp64 on the float32 pixels.
+// cc_rigk_start_dev.hpp -- the kernels of the pixel start (cc_rigk_start.hpp says what they are for) and their device helpers, in
+// a header so that cc_rigk_start.hip is the launches only. All arithmetic is fp64 on the float32 pixels.
 //
 // One wave per view: the view's camera and with it the intrinsics set are the same for every lane, so the set's 8 or 9
 // coefficients are scalar loads and live in scalar registers; lanes stride over the view's observations. A lane's result depends
@@ -82,11 +82,14 @@ __device__ __forceinline__ double rigk_fisheye_slope(const double* __restrict__ 
   return 1.0 + w * (3.0 * k[4] + w * (5.0 * k[5] + w * (7.0 * k[6] + w * (9.0 * k[7]))));
 }
 
-// theta in [0, pi/2) with theta_d(theta) = td > 0, by the rule of k_undistort_fisheye: a root bracketed by the interval's ends is
+// theta in [0, top) with theta_d(theta) = td > 0, by the rule of k_undistort_fisheye: a root bracketed by the interval's ends is
 // found by Newton steps that fall back to bisection; otherwise plain Newton from theta = td climbs the first rising branch and
 // either converges inside the interval or meets a slope <= 0 / leaves the interval / runs out of steps: no root.
+// top is the double below pi/2 for the normalised point x / z = tan(theta) (xd, yd) / td, and with BEYOND_90 the double below pi
+// for the bearing start: a point at 90 degrees off the axis and beyond it has a theta like any other; only tan(theta) had none.
+template <bool BEYOND_90>
 __device__ __forceinline__ bool rigk_fisheye_root(const double* __restrict__ k, double td, double* theta) {
-  const double top = 1.5707963267948966;   // the double below pi/2
+  const double top = BEYOND_90 ? 3.141592653589793 : 1.5707963267948966;
   const bool bracketed = rigk_fisheye_theta_d(k, top) - td > 0.0;
   double lo = 0.0, hi = top;
   double th = td < top ? td : 0.5 * top;
@@ -129,7 +132,45 @@ __global__ __launch_bounds__(64) void k_rigk_start_unproject(RigkStartDev P) {
         const double td = sqrt(xd * xd + yd * yd);
         double th;
         if (td == 0.0) o = make_float2((float)xd, (float)yd);   // the axis itself
-        else if (td > 0.0 && rigk_fisheye_root(k, td, &th)) {
+        else if (td > 0.0 && rigk_fisheye_root<false>(k, td, &th)) {
+          const double s = tan(th) / td;
+          o = make_float2((float)(xd * s), (float)(yd * s));
+        }
+      } else {
+        double x, y;
+        if (rigk_radtan_root(k, xd, yd, &x, &y)) o = make_float2((float)x, (float)y);
+      }
+    }
+    if (isnan(o.x) || isnan(o.y)) o = make_float2(nanf_, nanf_);   // (a non-finite coefficient: both coordinates or none)
+    out2[i] = o;
+  }
+}
+
+// ... with the model of the view's camera (CC_MODEL_MIXED): the model and the intrinsics set the same for every lane. The two
+// bodies stand next to each other: a per-view function shared between them, as rigk_bearing_view is, moves both kernels'
+// register allocation
+__global__ __launch_bounds__(64) void k_rigk_start_unproject_cam(RigkStartCamDev P) {
+  const int64_t g = blockIdx.x;
+  if (g >= P.NG) return;
+  const int64_t s0 = P.goff[g], s1 = P.goff[g + 1];
+  const int cam = P.gcam[g];
+  const bool fish = P.cmodel[cam] == CC_MODEL_FISHEYE;
+  const double* __restrict__ k = P.intr + (size_t)P.kset[cam] * 16;   // (the same for every lane: scalar loads)
+  const double fx = k[0], fy = k[1], px = k[2], py = k[3];
+  const bool focal_ok = isfinite(fx) && isfinite(fy) && fx != 0.0 && fy != 0.0;
+  const float2* __restrict__ uv2 = reinterpret_cast<const float2*>(P.uv);
+  float2* __restrict__ out2 = reinterpret_cast<float2*>(P.out);
+  const float nanf_ = __builtin_nanf("");
+  for (int64_t i = s0 + threadIdx.x; i < s1; i += 64) {
+    const float2 p = uv2[i];
+    float2 o = make_float2(nanf_, nanf_);
+    if (focal_ok && isfinite(p.x) && isfinite(p.y)) {
+      const double xd = ((double)p.x - px) / fx, yd = ((double)p.y - py) / fy;
+      if (fish) {
+        const double td = sqrt(xd * xd + yd * yd);
+        double th;
+        if (td == 0.0) o = make_float2((float)xd, (float)yd);   // the axis itself
+        else if (td > 0.0 && rigk_fisheye_root<false>(k, td, &th)) {
           const double s = tan(th) / td;
           o = make_float2((float)(xd * s), (float)(yd * s));
         }
@@ -144,33 +185,6 @@ __global__ __launch_bounds__(64) void k_rigk_start_unproject(RigkStartDev P) {
 }
 
 // ---- the bearing start: unit directions instead of x / z ------------------------------------------------------------------------
-// rigk_fisheye_root with the interval [0, pi): the same rule, the bracket's far end at the double below pi. A point at 90 degrees
-// off the axis and beyond it has a theta like any other; only tan(theta) had none.
-__device__ __forceinline__ bool rigk_fisheye_root_pi(const double* __restrict__ k, double td, double* theta) {
-  const double top = 3.141592653589793;   // the double below pi
-  const bool bracketed = rigk_fisheye_theta_d(k, top) - td > 0.0;
-  double lo = 0.0, hi = top;
-  double th = td < top ? td : 0.5 * top;
-  bool found = false;
-  for (int it = 0; it < 200; ++it) {
-    const double f = rigk_fisheye_theta_d(k, th) - td;
-    const double fp = rigk_fisheye_slope(k, th);
-    if (f == 0.0) { found = true; break; }
-    double tn = th - f / fp;
-    if (bracketed) {
-      if (f > 0.0) hi = th; else lo = th;
-      if (!(fp > 0.0) || !(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
-    } else if (!(fp > 0.0) || !(tn >= 0.0 && tn <= top)) {
-      break;
-    }
-    const bool small = fabs(tn - th) <= 4.5e-16 * th;
-    th = tn;
-    if (small) { found = true; break; }
-  }
-  *theta = th;
-  return found || bracketed;
-}
-
 // One view's pixels into float3 unit bearings (three floats per observation, packed); NaN x 3: no bearing.
 __device__ __forceinline__ void rigk_bearing_view(const RigkBearingDev& P, int64_t g, bool fish, const double* __restrict__ k) {
   const int64_t s0 = P.goff[g], s1 = P.goff[g + 1];
@@ -188,7 +202,7 @@ __device__ __forceinline__ void rigk_bearing_view(const RigkBearingDev& P, int64
         const double td = sqrt(xd * xd + yd * yd);
         double th;
         if (td == 0.0) { o0 = 0.0f; o1 = 0.0f; o2 = 1.0f; }   // the axis itself
-        else if (td > 0.0 && rigk_fisheye_root_pi(k, td, &th)) {
+        else if (td > 0.0 && rigk_fisheye_root<true>(k, td, &th)) {
           const double s = sin(th) / td;
           o0 = (float)(xd * s); o1 = (float)(yd * s); o2 = (float)cos(th);
         }

@@ -533,7 +533,7 @@ int cc_rigk_get_camera_intrinsics(cc_rig* h, int64_t camera, double* intr9);
  * its own (cc_rigk_set_camera_model below).
  * Fisheye: the slots are fx fy px py k1 k2 k3 k4 -; cc_rigk_set_intrinsics / _set_camera_intrinsics force bit 8 of the
  * constant mask and store 0 in slot 8. A CHANGE of the model drops the captured graphs and the intrinsics (the next solve
- * needs cc_rigk_set_intrinsics again) and puts the handle on the tile form of the sweep (k_rig_sweep_adjk_fisheye: there is
+ * needs cc_rigk_set_intrinsics again) and puts the handle on the tile form of the sweep (k_rig_sweep_lens: there is
  * no compact-record form, whatever the group size and CC_RIG_K_COMPACT). Setting the model the handle has is a no-op; a
  * handle that never leaves CC_MODEL_RADTAN launches the kernels it always did. Large rigs (<= 255 shared coordinates),
  * cc_rig_eval / _reset / _solver_status and profiled rounds work as on any cc_rigk_* handle.
@@ -554,7 +554,7 @@ int cc_rigk_get_model(cc_rig* h, int32_t* model);
  * A handle all of whose cameras have one model IS the homogeneous handle of that model, however it got there: it launches the
  * kernels such a handle launches and returns the same bits. A handle whose cameras differ sweeps into tiles (no compact-record
  * form, whatever the group size and CC_RIG_K_COMPACT) with ONE LAUNCH PER MODEL that has an observed camera
- * (k_rig_sweep_adjk_sel): under profile_kernels a sweep then counts two launches of CC_K_SWEEP in kernel_launches while
+ * (k_rig_sweep_lens): under profile_kernels a sweep then counts two launches of CC_K_SWEEP in kernel_launches while
  * `sweeps` stays one per round. Large rigs, cc_rig_eval / _reset / _solver_status / _get_state, profiled rounds and
  * cc_rigk_estimate_start (every pixel through the inverse of ITS camera's model) work. A camera without observations keeps
  * its recorded model.

@@ -6,7 +6,7 @@ sides of every comparison alternating inside one process. All sides see the same
 Steps, each a child process of its own under `timeout` (a step that fails or runs out of time ends the script; nothing is
 started behind it):
   pair CxFxP [per_camera] -- three handles alternating: radial-tangential in the tile form (CC_RIG_K_COMPACT=0, k_rig_sweep_adjk),
-                fisheye (k_rig_sweep_adjk_fisheye: always tiles) and the DEFAULT radial-tangential handle (k_rig_sweep_k2 from
+                fisheye (k_rig_sweep_lens: always tiles) and the DEFAULT radial-tangential handle (k_rig_sweep_k2 from
                 ~450 observations per group on). fisheye / tile is the model's own cost, fisheye / default what a fisheye user
                 gives up by having no compact-record form;
   radtan_only, with --baseline-lib PATH -- the default radial-tangential handle alone at the first shape, --pairs times with the

@@ -5,9 +5,9 @@ radial-tangential and the odd ones fisheye, each camera solving pixels of its ow
 
 Steps, each a child process of its own under `timeout` (a step that fails or runs out of time ends the script; nothing is
 started behind it):
-  quad CxFxP    -- four handles alternating: the mixed handle (k_rig_sweep_adjk_sel, one launch per model), the homogeneous
+  quad CxFxP    -- four handles alternating: the mixed handle (k_rig_sweep_lens over a list, one launch per model), the homogeneous
                 radial-tangential handle in the tile form (CC_RIG_K_COMPACT=0, k_rig_sweep_adjk), the homogeneous fisheye handle
-                (k_rig_sweep_adjk_fisheye) and the DEFAULT radial-tangential handle (k_rig_sweep_k2 from ~450 observations per
+                (k_rig_sweep_lens without a list) and the DEFAULT radial-tangential handle (k_rig_sweep_k2 from ~450 observations per
                 group on). The mixed handle does half the groups of each tile form and pays one launch more per round;
   radtan_only, with --baseline-lib PATH -- the default radial-tangential handle alone at the first shape, --pairs times with the
                 other build of the library (the parent commit's) and with this one, alternating: the existing path did not move

@@ -1,5 +1,5 @@
 """CPU reference of the rig solve with intrinsics with a pixel model PER CAMERA (cc_rigk_set_camera_model; the kernels:
-cc_rig_mixed.hip): tests/rigk_fisheye_ref.py's problem with the rows of camera c taken from models[c], its LM (rigk_solve) run on it
+cc_rig_lens.hip): tests/rigk_fisheye_ref.py's problem with the rows of camera c taken from models[c], its LM (rigk_solve) run on it
 unchanged, and the scenarios of tests/test_rigk_mixed_cpu.py / tests/test_gpu_rigk_mixed.py. Shares no code with the kernels.
 A helper module, not a test. Callers must not modify what they get."""
 import functools

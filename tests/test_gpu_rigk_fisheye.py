@@ -1,5 +1,5 @@
 """EXTENSION: the fisheye (Kannala-Brandt) camera model of the rig solve with intrinsics (cc_rigk_set_model; the kernels:
-cc_rig_fisheye.hip). The checker is tests/rigk_fisheye_ref.py: the rig-with-intrinsics LM restated in numpy with a pluggable pixel
+cc_rig_lens.hip). The checker is tests/rigk_fisheye_ref.py: the rig-with-intrinsics LM restated in numpy with a pluggable pixel
 model, itself pinned on the CPU (tests/test_rigk_fisheye_cpu.py) against the oracle, the 50-digit model and scipy.
 
 Bounds (the project's standing ones for this path): identical termination, iteration count, accept / valid sequence; logged

@@ -1,5 +1,5 @@
 """EXTENSION: a pixel model per camera on one rig handle with intrinsics (cc_rigk_set_camera_model / _get_camera_model; the
-kernels: cc_rig_mixed.hip). The checker is tests/rigk_mixed_ref.py -- tests/rigk_fisheye_ref.py's LM on a problem whose rows come
+kernels: cc_rig_lens.hip). The checker is tests/rigk_mixed_ref.py -- tests/rigk_fisheye_ref.py's LM on a problem whose rows come
 from each camera's own model -- itself pinned on the CPU (tests/test_rigk_mixed_cpu.py).
 
 Bounds (the project's standing ones for this path): identical termination, iteration count, accept / valid
@@ -165,6 +165,40 @@ def test_group_grams_of_each_model(name, monkeypatch):
                 assert np.array_equal(got[15], np.zeros(16)) and np.array_equal(got[:, 15], np.zeros(16))
             else:
                 assert got[15, 15] > 0.0 and w[15, 15] > 0.0
+
+
+def test_fisheye_groups_through_the_list_and_without_it_leave_the_same_bits(monkeypatch):
+    """k_rig_sweep_lens<NW, fisheye, true> against <NW, fisheye, false>. ffr_unseen: cameras 0 and 1 are fisheye, camera 2 is
+    radial-tangential and unobserved, so the handle is a mixed one and every group is a fisheye group reached through the list.
+    A second handle on the same observations, start state and intrinsics with set_model(MODEL_FISHEYE) is the homogeneous one
+    and sweeps without a list. A group's Gram depends on its own observations and its camera, frame and intrinsics records only
+    (whatever the fisheye slot rule does to the unobserved camera 2's set stays outside them), so the first 256 doubles of every
+    group's record for the starting point are the same bits, in both workgroup forms."""
+    k, pk, _ = mr.gpu_case("ffr_unseen")
+    groups = mr.groups(k)
+    assert k["kinds"] == "FFR" and len(groups) > 0 and {c for _, c, _ in groups} == {0, 1}
+
+    def grams(homogeneous):
+        if homogeneous:
+            prob = _create(k, pk.get("huber_a", 0.0))
+            prob.set_model(capi.MODEL_FISHEYE)
+            _set_intrinsics(prob, k, pk.get("const_masks"))
+            prob.set_state(k["cam_q0"], k["cam_t0"], k["frame_q0"], k["frame_t0"])
+        else:
+            prob = _problem(k, **pk)
+        assert prob.get_model() == (capi.MODEL_FISHEYE if homogeneous else capi.MODEL_MIXED)
+        prob.solve(capi.default_options(max_iterations=1))
+        rec = _fetch(prob, "gcomp", len(groups) * 320).reshape(len(groups), 320)
+        prob.close()
+        return rec[:, :256].copy()
+
+    for waves in (4, 1):
+        monkeypatch.setenv("CC_RIG_SWEEP_WG_WAVES", str(waves))
+        listed, plain = grams(False), grams(True)
+        assert np.all(np.isfinite(listed)) and np.abs(listed).max() > 0.0
+        differ = int((listed != plain).sum())
+        print("ffr_unseen, %d wave(s): %d groups, %d of %d doubles differ between the list and the no-list sweep" % (waves, len(groups), differ, listed.size))
+        assert np.array_equal(listed, plain)
 
 
 # ---- 4. cameras without observations --------------------------------------------------------------------------------------------
