@@ -56,6 +56,31 @@ class Iteration(C.Structure):
     ]
 
 
+class IntrStartOptions(C.Structure):
+    """cc_intr_start_options: the fisheye focal-length start (cc_intrinsics_estimate_start_fisheye)."""
+    _fields_ = [
+        ("centre", C.c_double * 2),
+        ("theta_lo", C.c_double),
+        ("theta_hi", C.c_double),
+        ("candidates", C.c_int32),
+        ("search_views", C.c_int32),
+        ("refine_iterations", C.c_int32),
+    ]
+
+
+class IntrStartReport(C.Structure):
+    _fields_ = [
+        ("centre", C.c_double * 2),
+        ("r_max", C.c_double),
+        ("focal", C.c_double),
+        ("best_candidate", C.c_int32),
+        ("candidates_qualified", C.c_int32),
+        ("views", C.c_int64),
+        ("views_searched", C.c_int64),
+        ("views_invalid", C.c_int64),
+    ]
+
+
 class Summary(C.Structure):
     _fields_ = [
         ("iterations", C.c_int32),
@@ -95,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "cc_intrinsics_set_model", "cc_intrinsics_get_model", "cc_intrinsics_optimize_views_model", "cc_intrinsics_estimate_views_model",
     "cc_distort_fisheye", "cc_undistort_fisheye",
     "cc_intrinsics_batch_set_model", "cc_intrinsics_batch_get_model", "cc_intrinsics_batch_estimate_model",
+    "cc_intr_start_options_init", "cc_intrinsics_estimate_start_fisheye", "cc_intrinsics_start_scores", "cc_intrinsics_estimate_views_start",
 ]
 # EXTENSION: camera models of the single-camera solve (cc_solver.h)
 MODEL_RADTAN, MODEL_FISHEYE = 0, 1
@@ -147,6 +173,21 @@ def default_options(**kw):
         if not hasattr(o, k):
             raise AttributeError(k)
         setattr(o, k, v)
+    return o
+
+
+def intr_start_options(**kw):
+    """cc_intr_start_options with the library's defaults (centre NaN NaN: the pixels' bounding box, theta_lo 0.3, theta_hi 3.0,
+    candidates 24, search_views 32, refine_iterations 3) and the given fields; centre takes a pair."""
+    o = IntrStartOptions()
+    lib().cc_intr_start_options_init(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        if k == "centre":
+            o.centre[0], o.centre[1] = float(v[0]), float(v[1])
+        else:
+            setattr(o, k, v)
     return o
 
 
@@ -267,6 +308,29 @@ class IntrinsicsProblem:
         _check(lib().cc_intrinsics_obs_cost(self._h, _p(out, C.c_double)))
         return out
 
+    def estimate_start_fisheye(self, **options):
+        """EXTENSION: a start of the fisheye solve from the handle's own pixels (cc_intrinsics_estimate_start_fisheye): a search
+        over the focal length of the equidistant lens on bearing vectors, then every view's pose at the picked one. `options`:
+        the fields of cc_intr_start_options (intr_start_options). Returns (intr [9] = f f cx cy 0 .., q [F, 4], t [F, 3], report);
+        the handle's state is not touched: call set_state next."""
+        o = intr_start_options(**options)
+        intr, q, t = np.zeros(9), np.zeros((self.n_frames, 4)), np.zeros((self.n_frames, 3))
+        r = IntrStartReport()
+        _check(lib().cc_intrinsics_estimate_start_fisheye(self._h, C.byref(o), _p(intr, C.c_double), _p(q, C.c_double),
+                                                          _p(t, C.c_double), C.byref(r)))
+        report = {k: getattr(r, k) for k, _ in IntrStartReport._fields_ if k != "centre"}
+        report["centre"] = (r.centre[0], r.centre[1])
+        return intr, q, t, report
+
+    def start_scores(self):
+        """(f [C], score [C], qualified [C]) of the last estimate_start_fisheye's search (cc_intrinsics_start_scores): the
+        candidate focal lengths, S_j = f_j^2 sum of the searched views' chord costs, and whether candidate j placed every view
+        some candidate places."""
+        f, score, qualified = np.zeros(64), np.zeros(64), np.full(64, -1, dtype=np.int32)
+        _check(lib().cc_intrinsics_start_scores(self._h, _p(f, C.c_double), _p(score, C.c_double), _p(qualified, C.c_int32)))
+        n = int((qualified >= 0).sum())   # (the library writes 0 or 1 for every candidate of the search, and only those)
+        return f[:n].copy(), score[:n].copy(), qualified[:n].copy()
+
     def profile_sweep(self, n=50):
         ms = C.c_double()
         _check(lib().cc_intrinsics_profile_sweep(self._h, C.c_int32(n), C.byref(ms)))
@@ -380,12 +444,19 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
 
 
 def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, options=None, device=0, log_capacity=1024,
-                        views=False, huber_a=0.0, model=0):
+                        views=False, huber_a=0.0, model=0, start="zhang", start_options=None):
     """cc_intrinsics_estimate (= Calibrator::Estimate: Zhang initialisation + solve, one upload; views=True:
     cc_intrinsics_estimate_views, every view handed over as its own array and packed by the library under its upload;
     huber_a > 0: the extension cc_intrinsics_estimate_views_huber, views handed over as their own arrays; model != 0: the
     extension cc_intrinsics_estimate_views_model, likewise, `distortion5` then holding the model's coefficients).
+    start="fisheye": the extension cc_intrinsics_estimate_views_start, the focal-length search of estimate_start_fisheye in
+    place of Zhang's initialisation (model must be MODEL_FISHEYE; start_options: a dict of cc_intr_start_options fields or an
+    IntrStartOptions); start="zhang", the default, is the call as it was.
     Returns (K_init float32 3x3, intr, q, t, summary)."""
+    if start not in ("zhang", "fisheye"):
+        raise ValueError(f"start must be 'zhang' or 'fisheye', not {start!r}")
+    if start == "zhang" and start_options is not None:
+        raise ValueError("start_options belong to start='fisheye'")
     off = np.ascontiguousarray(frame_offsets, dtype=np.int64)
     F = len(off) - 1
     uv, xyz = _f32(uv), _f32(xyz)
@@ -397,6 +468,15 @@ def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, 
     K = np.zeros(9, dtype=np.float32)
     intr, q, t = np.zeros(9), np.zeros((F, 4)), np.zeros((F, 3))
     d5 = _f64(distortion5) if distortion5 is not None else None
+    if start == "fisheye":
+        so = start_options if isinstance(start_options, IntrStartOptions) else intr_start_options(**(start_options or {}))
+        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
+        _check(lib().cc_intrinsics_estimate_views_start(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
+                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
+                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
+                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
+                                                        C.c_int32(model), C.byref(so)))
+        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
     if model != 0:   # (0 is off: the symbols without a model argument, below)
         uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
         _check(lib().cc_intrinsics_estimate_views_model(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,

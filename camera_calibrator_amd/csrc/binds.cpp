@@ -138,6 +138,9 @@ PYBIND11_MODULE(pycalibrator, m) {
   py::enum_<calibrator::CameraModel>(m, "CameraModel")   // extension: lens models of Calibrator::SetCameraModel
       .value("RadTan", calibrator::CameraModel::RadTan)
       .value("Fisheye", calibrator::CameraModel::Fisheye);
+  py::enum_<calibrator::Start>(m, "Start")   // extension: where Estimate starts from (Calibrator::SetStart)
+      .value("Zhang", calibrator::Start::Zhang)
+      .value("FisheyeFocalSearch", calibrator::Start::FisheyeFocalSearch);
   py::class_<Calibrator>(m, "Calibrator")
       .def(py::init<int, int>())
       .def("EstimateOpenCv", &Calibrator::EstimateOpenCv, py::arg("img_points"), py::arg("world_points"))
@@ -157,6 +160,9 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("GetHuberLoss", &Calibrator::GetHuberLoss)
       .def("SetCameraModel", &Calibrator::SetCameraModel, py::arg("model"))   // extension: CameraModel.Fisheye = Kannala-Brandt
       .def("GetCameraModel", &Calibrator::GetCameraModel)
+      .def("SetStart", &Calibrator::SetStart, py::arg("start"))   // extension: Start.FisheyeFocalSearch with CameraModel.Fisheye
+      .def("GetStart", &Calibrator::GetStart)
+      .def("LastStartFocal", &Calibrator::LastStartFocal)
       .def("LastStatus", &Calibrator::LastStatus)
       .def("LastIterations", &Calibrator::LastIterations)
       .def("LastSolverReruns", &Calibrator::LastSolverReruns)

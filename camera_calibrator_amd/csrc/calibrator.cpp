@@ -106,6 +106,10 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     throw std::invalid_argument("Calibrator::Estimate: the Huber loss (SetHuberLoss) is for one device; SetDevices selected several");
   if (devices_.size() > 1 && model_ != CameraModel::RadTan)
     throw std::invalid_argument("Calibrator::Estimate: the fisheye model (SetCameraModel) is for one device; SetDevices selected several");
+  const bool focal_search = start_ == Start::FisheyeFocalSearch;
+  if (focal_search && model_ != CameraModel::Fisheye)
+    throw std::invalid_argument("Calibrator::Estimate: the focal-length search (SetStart) is a start of the fisheye model (SetCameraModel)");
+  last_start_focal_ = 0.0;
   if (devices_.size() <= 1) {
     // one device: the fused entry point (one upload of the observations for initialisation and solve together);
     // same numbers as the two calls below exchange through camera_matrix_ and the float poses. The views go over as they
@@ -127,6 +131,15 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     cc_options options;
     cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
     cc_summary summary{};
+    if (focal_search) {   // EXTENSION: the same call with the start chosen
+      cc_intr_start_options start;
+      cc_intr_start_options_init(&start);
+      for (float& v : K9) v = 0.0f;
+      last_status_ = cc_intrinsics_estimate_views_start(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+                                                        dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_,
+                                                        static_cast<int32_t>(model_), &start);
+      last_start_focal_ = K9[0];
+    } else
     last_status_ = cc_intrinsics_estimate_views_model(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
                                                       dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_,
                                                       static_cast<int32_t>(model_));   // (0, RadTan: cc_intrinsics_estimate_views)
@@ -199,6 +212,10 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   }
   const size_t F = foff.size() - 1;
   const CameraModel model = calibrators[0]->model_;
+  for (size_t p = 0; p < B; ++p)
+    if (calibrators[p]->start_ != Start::Zhang)
+      throw std::invalid_argument("Calibrator::EstimateMany: a calibrator has the focal-length search set (SetStart); the batch starts from "
+                                  "Zhang's initialisation -- call Estimate on that calibrator");
   for (size_t p = 1; p < B; ++p)   // (refused before anything is packed)
     if (calibrators[p]->model_ != model)
       throw std::invalid_argument("Calibrator::EstimateMany: some calibrators have the fisheye model set (SetCameraModel) and some the "
@@ -349,6 +366,11 @@ void Calibrator::WriteBackDistortion(const double* intr) {
   const int n = model_ == CameraModel::Fisheye ? 4 : 5;
   if (distortion_.size() != n) distortion_ = DynamicVector::Zero(n);
   for (int i = 0; i < n; ++i) distortion_(i) = static_cast<float>(intr[K1 + i]);
+}
+
+void Calibrator::SetStart(Start start) {
+  if (start != Start::Zhang && start != Start::FisheyeFocalSearch) throw std::invalid_argument("Calibrator::SetStart: unknown start");
+  start_ = start;
 }
 
 void Calibrator::SetCameraModel(const CameraModel model) {

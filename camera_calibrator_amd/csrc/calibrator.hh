@@ -14,6 +14,8 @@ namespace calibrator {
 
 /// EXTENSION: the lens models of Calibrator::SetCameraModel (values of cc_solver.h's CC_MODEL_*)
 enum class CameraModel : int { RadTan = 0, Fisheye = 1 };
+/// EXTENSION: where Estimate / EstimateOpenCv start from (Calibrator::SetStart)
+enum class Start : int { Zhang = 0, FisheyeFocalSearch = 1 };
 
 class Calibrator {
  public:
@@ -78,11 +80,23 @@ class Calibrator {
   /// EstimateOpenCv / Distort / Undistort. Fisheye is the Kannala-Brandt / cv::fisheye model, theta_d = theta (1 + k1 theta^2 +
   /// k2 theta^4 + k3 theta^6 + k4 theta^8) with theta the angle from the optical axis -- for lenses past ~100 degrees of field
   /// of view. Switching the model resets the distortion to zeros of the model's length (5, or 4 for Fisheye);
-  /// ForceDistortionToConstant then takes 0..3. Estimate still starts from Zhang's pinhole initialisation with k = 0. Combines
+  /// ForceDistortionToConstant then takes 0..3. Estimate starts from Zhang's pinhole initialisation with k = 0 unless SetStart says otherwise. Combines
   /// with SetHuberLoss. Like the loss: ONE device, several kernels per LM iteration (LastSolverForm() == 0); Optimize / Estimate
   /// throw std::invalid_argument when SetDevices selected several, EstimateMany when its calibrators differ in their model.
   void SetCameraModel(CameraModel model);
   CameraModel GetCameraModel() const { return model_; }
+  /// EXTENSION (the reference starts from Zhang's pinhole homographies): the start of Estimate / EstimateOpenCv. Zhang, the
+  /// default: the calls as they were. FisheyeFocalSearch, with SetCameraModel(Fisheye): a search over the focal length of the
+  /// equidistant lens on bearing vectors with every view's pose at the picked one (cc_intrinsics_estimate_views_start at the
+  /// library's default options), for boards that stand round the lens and beyond 90 degrees off its axis, where Zhang's start
+  /// costs several times the iterations or ends in a wrong basin. With the radial-tangential model Estimate throws
+  /// std::invalid_argument, and so it does when SetDevices selected several devices; EstimateMany throws when any of its
+  /// calibrators has the search set (the batch keeps Zhang). A view the search cannot place throws std::runtime_error naming it.
+  void SetStart(Start start);
+  Start GetStart() const { return start_; }
+  /// The focal length the last Estimate's search picked, in float32 as K holds it (the start's K is handed over as float32, like
+  /// Zhang's); 0 after a Zhang start.
+  double LastStartFocal() const { return last_start_focal_; }
   /// Status of the last Optimize: 0 or a negative cc_status. The reference has no error channel
   /// (ceres' summary is discarded), so Optimize itself never throws on solver failure.
   int LastStatus() const { return last_status_; }
@@ -100,7 +114,7 @@ class Calibrator {
   double LastFinalCost() const { return last_final_cost_; }
   /// Wall milliseconds of the last Estimate / Optimize: [0] packing the views into (cached, pinned) flat arrays when the
   /// class does it (several devices; on one device the library packs piece by piece under its upload and the time is
-  /// part of [2]), [1] solver handle + device arena (cached), [2] pack + upload, [3] Zhang initialisation (Estimate),
+  /// part of [2]), [1] solver handle + device arena (cached), [2] pack + upload, [3] Zhang initialisation or focal-length search (Estimate),
   /// [4] solve, [5] read-back + teardown, [6] the whole call.
   const double* LastTimingMs() const { return last_timing_ms_; }
 
@@ -111,6 +125,8 @@ class Calibrator {
   int device_{0};
   double huber_a_{0.0};
   CameraModel model_{CameraModel::RadTan};
+  Start start_{Start::Zhang};
+  double last_start_focal_{0.0};
   void WriteBackDistortion(const double* intr);
   std::vector<int> devices_;
   int last_status_{0};

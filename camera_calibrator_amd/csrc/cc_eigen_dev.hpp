@@ -59,6 +59,8 @@ __device__ __forceinline__ void jacobi_eigen(double (&A)[N][N], double (&V)[N][N
 // systems -- nothing next to the float32 H of Zhang's initialisation. A caller that keeps the vector in fp64 (the rig start)
 // passes shift = 0: the pivots then stay positive by the 1e-30 floor alone, which moves the last pivot of a matrix that is
 // singular up to rounding by a rounding error, and the iteration converges to the eigenvector of A itself.
+// (smallest_eigvec_settled in cc_intr_start_dev.hpp is a copy of this function at shift 0 that iterates until the vector settles:
+// a fix here belongs there too.)
 template <int N>
 __device__ __forceinline__ void smallest_eigvec(const double (&A)[N][N], double (&x)[N], double shift = 1e-14) {
   double sc[N];

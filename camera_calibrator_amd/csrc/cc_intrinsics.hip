@@ -967,6 +967,15 @@ struct cc_intrinsics : cc::SolveHost {   // pinned: a cached block, host_pub (16
   size_t p_box_bytes = 0;       // seam mailboxes (re-zeroed before the epochs wrap)
   double huber_a = 0.0;         // EXTENSION (cc_intrinsics_set_huber): > 0 -> HuberLoss(a), pixels; the handle then solves in the two-kernel form
   int model = CC_MODEL_RADTAN;  // EXTENSION (cc_intrinsics_set_model): CC_MODEL_FISHEYE -> k_intr_sweep_fisheye, two-kernel form, one device
+  // EXTENSION (cc_intrinsics_estimate_start_fisheye, cc_intr_start_host.hpp): the start's device scratch, an allocation of its
+  // own that grows on demand, and the candidates of the last search in it (0: none has run)
+  void* start_work = nullptr;
+  size_t start_work_bytes = 0;
+  int start_candidates = 0;
+  const double* start_srec = nullptr;   // the search's records [candidates][start_searched][24] and the pose pass's [F][24] in it
+  const double* start_view = nullptr;
+  int64_t start_searched = 0;
+  bool start_marks = false;             // scripts (cc_intrinsics_debug_start_marks): time the start's phases with hipEvents
   // the handle solves in the two-kernel form by choice, on one device (a loss or a model that only a sweep of its own carries)
   bool own_sweep() const { return huber_a > 0.0 || model != CC_MODEL_RADTAN; }
 };
@@ -1329,6 +1338,7 @@ void cc_intrinsics_destroy(cc_intrinsics* h) {
   for (auto e : h->events) hipEventDestroy(e);
   if (h->comm) cc::comm_destroy(h->comm);
   cc::exchange_release(h);
+  if (h->start_work) (void)hipFree(h->start_work);
   if (h->arena) cc::arena_put(h->device, h->arena, h->arena_cached);   // (the stream was synchronised above: nothing of this handle is in flight)
   cc::pinned_block_put(h->pinned);
   if (stream_ok) cc::stream_put(h->device, h->stream);   // idle and reusable
@@ -1776,7 +1786,8 @@ int cc_intrinsics_optimize_multi(const cc_options* opt, int32_t n_devices, const
   return rc;
 }
 
-// Scripts and tests only (not in the public header): copy of a device vector. name: "vec_solve" (timing marks of timing-only builds), "stats", "ctl".
+// Scripts and tests only (not in the public header): copy of a device vector. name: "vec_solve" (timing marks of timing-only builds), "stats", "ctl",
+// "start_records" / "start_views" (the records of the last cc_intrinsics_estimate_start_fisheye: its search, its pose pass).
 int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, int64_t n) {
   using namespace cc;
   if (!h || !name || !out || n < 0) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_debug_fetch: bad arguments");
@@ -1786,6 +1797,8 @@ int cc_intrinsics_debug_fetch(cc_intrinsics* h, const char* name, double* out, i
   if (k == "vec_solve") { src = h->d.vec_solve; cap = kVecSolve; }
   else if (k == "stats") { src = h->d.stats; cap = h->F * h->d.T * kStatsCols; }   // (timing builds of the persistent kernel: per-workgroup marks)
   else if (k == "ctl") { src = reinterpret_cast<const double*>(h->d.ctl_next); cap = sizeof(LmCtl) / 8; }   // (the device's control block, raw words: tests/test_gpu_intr_publish.py)
+  else if (k == "start_records" && h->start_candidates > 0) { src = h->start_srec; cap = (int64_t)h->start_candidates * h->start_searched * 24; }
+  else if (k == "start_views" && h->start_candidates > 0) { src = h->start_view; cap = h->F * 24; }
   if (!src || n > cap) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_debug_fetch: unknown buffer or too long");
   CC_HIP(hipSetDevice(h->device));
   CC_HIP(hipStreamSynchronize(h->stream));
@@ -2188,3 +2201,6 @@ int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t ran
 }
 
 }  // extern "C"
+
+// EXTENSION: the fisheye focal-length start (cc_intrinsics_estimate_start_fisheye and the one-shot call that takes a start)
+#include "cc_intr_start_host.hpp"

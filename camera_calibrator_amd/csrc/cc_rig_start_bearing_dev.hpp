@@ -61,6 +61,8 @@ __device__ __forceinline__ void start_view_sums_bearing(const float* bearing, co
 // output record. The closed form comes from b x (P y~) = 0: its Gram is sum (I - b b^T) (x) y~ y~^T over the 9 (planar) or 12
 // (general) unknowns of P, row-major, staged as the two rows e_k (x) y~ of an orthonormal tangent pair e_1, e_2 of b.
 // P.uv is not read.
+// (cc_intr_start_dev.hpp holds a second copy of this body and of start_view_sums_bearing, with the bearing formed from the pixel --
+// k_intr_start_view; one shared definition changes this kernel's text, DESIGN 4.19. A fix here belongs there too.)
 __global__ __launch_bounds__(64) void k_rig_start_view_bearing(RigStartDev P, const float* __restrict__ bearing, int refine_iterations) {
   __shared__ __attribute__((aligned(16))) double s_stage[kStageDoublesPerWave];
   const int lane = threadIdx.x;

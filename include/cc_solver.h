@@ -295,8 +295,8 @@ int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, in
  * slot 8 is unused: its bit of the constant mask is forced on and it reads back as 0.
  * The batch carries the model too (cc_intrinsics_batch_set_model below), and so does the rig solve with intrinsics
  * (cc_rigk_set_model). Out of scope: the persistent per-solve kernel, every
- * multi-GPU form, a fisheye-aware initialisation (cc_intrinsics_estimate_views_model starts from Zhang's pinhole K
- * and poses with k = 0), other models.
+ * multi-GPU form, other models. cc_intrinsics_estimate_views_model starts from Zhang's pinhole K and poses with k = 0; a
+ * start made for the lens is cc_intrinsics_estimate_start_fisheye below.
  * ------------------------------------------------------------------------------------------- */
 enum { CC_MODEL_RADTAN = 0, CC_MODEL_FISHEYE = 1 };
 /* The model of later cc_intrinsics_set_state / _eval / _solve / _reset / _get_state / _obs_cost calls; combines with
@@ -316,6 +316,62 @@ int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, in
                                        const float* const* xyz_views, const int64_t* counts, const double* distortion5,
                                        uint32_t const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
                                        cc_summary* summary, double huber_a, int32_t model);
+
+/* ---------------------------------------------------------------------------------------------
+ * EXTENSION (the reference starts every solve from Zhang's pinhole homographies, calibrator.cpp:47-66): a start of the FISHEYE
+ * solve from the problem's own pixels, for lenses whose boards stand round the lens and beyond 90 degrees off its axis, where the
+ * pinhole start puts the focal length and the centre far off and the solve takes several times the iterations or ends in a
+ * wrong basin. A search over the focal length f of the equidistant lens r = f theta -- the fisheye model at
+ * k = 0, fx = fy = f -- on the bearing form of the rig start (cc_rigk_estimate_start_bearing), on the device:
+ *   1. centre c: `centre` when both coordinates are finite, else the midpoint of the bounding box of all finite pixels;
+ *      r_max: the largest distance of a finite pixel from c.
+ *   2. candidates j = 0 .. C-1: theta_j = theta_lo + j (theta_hi - theta_lo) / (C - 1) (C = 1: theta_lo), f_j = r_max / theta_j.
+ *   3. searched views: all of them when search_views is 0 or >= F, else the S = search_views views floor(k F / S), k = 0 .. S-1.
+ *   4. per (searched view, candidate), one wave: the float32 pixel into an fp64 bearing, d = uv - c, theta = |d| / f_j,
+ *      b = (sin theta d / |d|, cos theta), the centre pixel (0, 0, 1); then the closed form from b x (P y~) = 0 and
+ *      `refine_iterations` Levenberg-Marquardt steps on the chord p / |p| - b, the arithmetic of cc_rigk_estimate_start_bearing's
+ *      views; cost = sum |p / |p| - b|^2 at the returned pose.
+ *   5. S_j = f_j^2 sum_v cost_{j,v} over the searched views in index order (pixel units: without f_j^2 the chord favours long
+ *      focal lengths). A candidate with a searched view it cannot place is disqualified, unless no candidate places that view.
+ *      The smallest S_j among the qualified candidates wins, the lowest index on ties.
+ *   6. every view's pose at the winner (the searched views come out again with the same bits).
+ * Out of scope: the batch (cc_intrinsics_batch_* keeps Zhang), the radial-tangential model, estimating k or a non-square pixel
+ * in the start, interpolation between candidates, multi-GPU handles, the persistent kernel; no entry point takes this start by
+ * default, and the rig solve does not take its result by itself (cc_rigk_set_intrinsics is the caller's second call).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct cc_intr_start_options {
+  double centre[2];          /* NaN (either): the bounding box's midpoint */
+  double theta_lo, theta_hi; /* the angle of the outermost pixel under the first and the last candidate: 0 < lo <= hi < pi */
+  int32_t candidates;        /* 1 .. 64 */
+  int32_t search_views;      /* 0: every view */
+  int32_t refine_iterations; /* 0 .. 1000 */
+} cc_intr_start_options;
+/* NaN, NaN, 0.3, 3.0, 24, 32, 3 */
+void cc_intr_start_options_init(cc_intr_start_options* o);
+typedef struct cc_intr_start_report {
+  double centre[2], r_max, focal;
+  int32_t best_candidate, candidates_qualified;
+  int64_t views, views_searched, views_invalid;
+} cc_intr_start_report;
+/* The start of a handle whose model is CC_MODEL_FISHEYE (any other handle, or one with an exchange or a communicator:
+ * CC_ERR_STATE). opt NULL: the defaults; candidates, theta_lo / theta_hi, search_views or refine_iterations out of range:
+ * CC_ERR_BAD_ARGUMENT. intr9 receives (f, f, c_x, c_y, 0, 0, 0, 0, 0), q_wxyz [4F] / t_xyz [3F] every view's pose; a view that
+ * is invalid by its own data (fewer than 4 points, collinear points, a non-finite pixel or point) is counted in
+ * report->views_invalid and gets q = (1, 0, 0, 0), t = 0. Every output may be NULL. No qualified candidate: CC_ERR_STATE, and
+ * nothing is written. The handle's state is not touched -- cc_intrinsics_set_state comes next, as after cc_zhang_init. */
+int cc_intrinsics_estimate_start_fisheye(cc_intrinsics* h, const cc_intr_start_options* opt, double* intr9, double* q_wxyz,
+                                         double* t_xyz, cc_intr_start_report* report);
+/* The last search of the handle: f [C], score [C] (S_j), qualified [C] (each may be NULL). CC_ERR_STATE before any start. */
+int cc_intrinsics_start_scores(cc_intrinsics* h, double* f, double* score, int32_t* qualified);
+/* cc_intrinsics_estimate_views_model with the start chosen. start NULL: that call, bit for bit (Zhang). Otherwise the model must
+ * be CC_MODEL_FISHEYE (CC_ERR_BAD_ARGUMENT), the start above replaces Zhang's, the distortion starts from `distortion5`'s four
+ * values (NULL: zeros), and K_init9 receives (f, 0, c_x; 0, f, c_y; 0, 0, 1). A view without a pose at the winner:
+ * CC_ERR_BAD_ARGUMENT, the message names the first such view (views of fewer than 4 points included: the start, not the
+ * packing, refuses them); no qualified candidate: CC_ERR_BAD_ARGUMENT too (there is no handle whose state it could be). */
+int cc_intrinsics_estimate_views_start(const cc_options* opt, int32_t device, int64_t n_frames, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5,
+                                       uint32_t const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summary, double huber_a, int32_t model, const cc_intr_start_options* start);
 
 /* ---------------------------------------------------------------------------------------------
  * EXTENSION (nothing in the reference does it): a BATCH of independent single-camera problems solved together on one
