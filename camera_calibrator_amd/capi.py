@@ -117,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "cc_intrinsics_batch_solve", "cc_intrinsics_batch_optimize", "cc_intrinsics_batch_estimate",
     "cc_intrinsics_set_huber", "cc_intrinsics_obs_cost", "cc_intrinsics_optimize_views_huber", "cc_intrinsics_estimate_views_huber",
     "cc_intrinsics_batch_set_huber", "cc_intrinsics_batch_estimate_huber",
+    "cc_intrinsics_set_final_sweep", "cc_intrinsics_final_sweep_counts",
     "cc_intrinsics_set_model", "cc_intrinsics_get_model", "cc_intrinsics_optimize_views_model", "cc_intrinsics_estimate_views_model",
     "cc_distort_fisheye", "cc_undistort_fisheye",
     "cc_intrinsics_batch_set_model", "cc_intrinsics_batch_get_model", "cc_intrinsics_batch_estimate_model",
@@ -291,6 +292,17 @@ class IntrinsicsProblem:
         """EXTENSION: ceres::HuberLoss(a), a in pixels, for later eval / solve / obs_cost calls (cc_intrinsics_set_huber);
         a <= 0 switches it off. With it on the handle solves in the two-kernel form."""
         _check(lib().cc_intrinsics_set_huber(self._h, C.c_double(a)))
+
+    def set_final_sweep(self, mode):
+        """The sweep of a persistent solve's last round (cc_intrinsics_set_final_sweep): 0 always full, 1 residual-only where the
+        control predicts that the round's decision ends the solve (the default), 2 predicted at every accepting decision (tests)."""
+        _check(lib().cc_intrinsics_set_final_sweep(self._h, C.c_int32(mode)))
+
+    def final_sweep_counts(self):
+        """(residual_only, redone) of the last persistent solve (cc_intrinsics_final_sweep_counts)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        _check(lib().cc_intrinsics_final_sweep_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def set_model(self, model):
         """EXTENSION: the camera model of later set_state / eval / solve / obs_cost calls (cc_intrinsics_set_model):

@@ -965,6 +965,7 @@ struct cc_intrinsics : cc::SolveHost {   // pinned: a cached block, host_pub (16
   cc::PersistDev pq{};
   uint32_t p_epoch = 0;         // last epoch handed to a launch (the seam words only ever see growing epochs)
   size_t p_box_bytes = 0;       // seam mailboxes (re-zeroed before the epochs wrap)
+  int final_sweep = 1;          // cc_intrinsics_set_final_sweep: what PersistDev::final_sweep says to the next persistent solves
   double huber_a = 0.0;         // EXTENSION (cc_intrinsics_set_huber): > 0 -> HuberLoss(a), pixels; the handle then solves in the two-kernel form
   int model = CC_MODEL_RADTAN;  // EXTENSION (cc_intrinsics_set_model): CC_MODEL_FISHEYE -> k_intr_sweep_fisheye, two-kernel form, one device
   // EXTENSION (cc_intrinsics_estimate_start_fisheye, cc_intr_start_host.hpp): the start's device scratch, an allocation of its
@@ -1207,7 +1208,7 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   const size_t o_ss = take(16 * sizeof(double));
   const size_t o_ctl = take(sizeof(LmCtl));
   const size_t o_ctln = take(sizeof(LmCtl));
-  const size_t o_sync = take(64);                     // arrival counter (+0), published-chunk counter (+8)
+  const size_t o_sync = take(64);                     // arrival counter (+0), published-chunk counter (+8), final-sweep counts of the last persistent solve (+16, +20)
   const size_t o_opts = take(sizeof(LmOpts));
   const size_t o_iintr = take(16 * sizeof(double));
   const size_t o_ipose = take((size_t)F * 8 * sizeof(double));
@@ -1304,6 +1305,7 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   h->pq.xbox = reinterpret_cast<unsigned long long*>(base + o_xbox);
   h->pq.fail = reinterpret_cast<unsigned*>(base + o_pfail);
   h->pq.lbox = reinterpret_cast<unsigned long long*>(base + o_lbox);
+  h->pq.fs_counts = reinterpret_cast<unsigned*>(base + o_sync + 16);
   h->pq.G = (int32_t)PG;
   h->pq.teams = p_teams;
   h->p_epoch = 0;
@@ -1448,6 +1450,32 @@ int cc_intrinsics_set_huber(cc_intrinsics* h, double a_pixels) {
   const double a = a_pixels > 0.0 ? a_pixels : 0.0;
   if (a != h->huber_a) drop_graphs(h);   // kernel and arguments are baked into the graphs
   h->huber_a = a;
+  return CC_OK;
+}
+
+// The sweep of a persistent solve's last round (cc_intrinsics_persist.hip): 0 every sweep full, 1 residuals only where the control
+// predicts that the round's decision ends the solve (the default), 2 predicted at every accepting decision (tests: the wrong
+// prediction's path on every round). The results do not depend on it. A kernel argument: no captured graph holds it.
+int cc_intrinsics_set_final_sweep(cc_intrinsics* h, int32_t mode) {
+  using namespace cc;
+  if (!h) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_final_sweep: NULL handle");
+  if (mode < 0 || mode > 2) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_set_final_sweep: mode %d is not 0, 1 or 2", (int)mode);
+  h->final_sweep = mode;
+  return CC_OK;
+}
+
+// ... and what the last persistent solve made of it: rounds swept residual-only, and those of them whose decision accepted the
+// candidate without ending the solve, so that the workers swept it again in full. Zeros before the first persistent solve; a solve
+// in the two-kernel form leaves them alone.
+int cc_intrinsics_final_sweep_counts(cc_intrinsics* h, int32_t* residual_only, int32_t* redone) {
+  using namespace cc;
+  if (!h || !residual_only || !redone) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_final_sweep_counts: NULL argument");
+  CC_HIP(hipSetDevice(h->device));
+  unsigned w[2] = {0u, 0u};
+  CC_HIP(hipMemcpyAsync(w, h->pq.fs_counts, sizeof(w), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipStreamSynchronize(h->stream));
+  *residual_only = (int32_t)w[0];
+  *redone = (int32_t)w[1];
   return CC_OK;
 }
 
@@ -1598,6 +1626,7 @@ static int persistent_launch(cc_intrinsics* h, SolveRun* r) {
   h->p_epoch += need;
   q.timeout_shift = h->exchange ? 30 : 27;
   q.first_shift = h->exchange ? 30 : 20;
+  q.final_sweep = h->final_sweep;
   // (CC_INTR_PERSIST_TEST_NO_CONTROL: test hook for the rerun in the two-kernel form, tests/test_gpu_intrinsics.py)
   static int drop_left = -2;
   const bool drop_control = !h->exchange && persist_test_drop_control("CC_INTR_PERSIST_TEST_NO_CONTROL", &drop_left);

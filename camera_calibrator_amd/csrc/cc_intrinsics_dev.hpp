@@ -119,6 +119,74 @@ __device__ __forceinline__ void row_v(const double* k, const ObsCommon& c, doubl
 // entry e = 16 row + col of a frame's 16 x 16 Gram block: does it belong to a coordinate held constant (mask bit j = intrinsic j)?
 __device__ __forceinline__ bool gram_entry_held(uint32_t mask, int e) { return (((mask >> (e >> 4)) | (mask >> (e & 15))) & 1u) != 0; }
 
+// obs_common with every fused multiply-add SPELLED OUT, the way the sweeps' main loops are compiled (cc_intrinsics_huber.hpp has the
+// account), and both residual components behind it: what a loop needs that evaluates the residuals without the rows -- the robust
+// sweeps (the loss weighs a row by both) and the residual-only sweep of k_intr_persist, whose cost must have the full sweep's bits.
+// (ONE_TEAM: the choices of k_intr_persist<1>, which fuses the rotation's first two rows the other way round -- its solves are on
+// record bit for bit, tests/golden/intr_*_parent.npz, like those of the other forms.)
+template <bool ONE_TEAM = false>
+__device__ __forceinline__ void huber_obs_common(const double* k, const double* R, const double* t,
+                                                 double X0, double X1, double X2, ObsCommon& c) {
+#pragma clang fp contract(off)
+  c.a0 = ONE_TEAM ? fma(R[2], X2, fma(R[0], X0, R[1] * X1)) : fma(R[2], X2, fma(R[1], X1, R[0] * X0));
+  c.a1 = ONE_TEAM ? fma(R[5], X2, fma(R[4], X1, R[3] * X0)) : fma(R[5], X2, fma(R[3], X0, R[4] * X1));
+  c.a2 = fma(R[8], X2, fma(R[6], X0, R[7] * X1));
+  const double xc = c.a0 + t[0], yc = c.a1 + t[1], zc = c.a2 + t[2];
+  c.iz = 1.0 / zc;
+  c.x = xc * c.iz;
+  c.y = yc * c.iz;
+  const double k1 = k[4], k2 = k[5], p1 = k[6], p2 = k[7], k3 = k[8];
+  const double xx = c.x * c.x, yy = c.y * c.y;
+  c.xy = c.x * c.y;
+  c.r2 = fma(c.y, c.y, xx);
+  c.r4 = c.r2 * c.r2;
+  c.r6 = c.r4 * c.r2;
+  const double m = fma(k3, c.r6, fma(k2, c.r4, fma(k1, c.r2, 1.0)));
+  c.ax = fma(2.0, xx, c.r2);
+  c.ay = fma(2.0, yy, c.r2);
+  c.xd = fma(p2, c.ax, fma(2.0 * p1, c.xy, c.x * m));
+  c.yd = fma(p1, c.ay, fma(2.0 * p2, c.xy, c.y * m));
+  const double mp2 = 2.0 * fma(3.0 * k3, c.r4, fma(2.0 * k2, c.r2, k1));
+  c.dxx = fma(6.0 * p2, c.x, fma(2.0 * p1, c.y, fma(mp2, xx, m)));
+  c.dxy = fma(2.0 * p2, c.y, fma(2.0 * p1, c.x, mp2 * c.xy));
+  c.dyy = fma(6.0 * p1, c.y, fma(2.0 * p2, c.x, fma(mp2, yy, m)));
+}
+
+// the pose columns and the residual behind a row's first nine entries: b0, b1 = d r / d (x, y) / z, b2 the z column
+__device__ __forceinline__ void huber_row_tail(const ObsCommon& c, double b0, double b1, double b2, double rw, double* v) {
+#pragma clang fp contract(off)
+  v[9] = 2.0 * fma(b2, c.a1, -(b1 * c.a2)); v[10] = 2.0 * fma(b0, c.a2, -(b2 * c.a0)); v[11] = 2.0 * fma(b1, c.a0, -(b0 * c.a1));
+  v[12] = b0; v[13] = b1; v[14] = b2; v[15] = rw;
+}
+
+// row_u / row_v with the residual r handed in (huber_residuals) and the weight w on the row's factors, as there
+__device__ __forceinline__ void huber_row_u(const double* k, const ObsCommon& c, double r, double* v, double w) {
+#pragma clang fp contract(off)
+  const double fx = k[0] * w;
+  v[0] = c.xd * w; v[1] = 0.0; v[2] = w; v[3] = 0.0;
+  const double fxx = fx * c.x;
+  v[4] = fxx * c.r2; v[5] = fxx * c.r4; v[6] = fx * 2.0 * c.xy; v[7] = fx * c.ax; v[8] = fxx * c.r6;
+  const double b0 = fx * c.dxx * c.iz, b1 = fx * c.dxy * c.iz, b2 = -fma(b1, c.y, b0 * c.x);
+  huber_row_tail(c, b0, b1, b2, r * w, v);
+}
+
+__device__ __forceinline__ void huber_row_v(const double* k, const ObsCommon& c, double r, double* v, double w) {
+#pragma clang fp contract(off)
+  const double fy = k[1] * w;
+  v[0] = 0.0; v[1] = c.yd * w; v[2] = 0.0; v[3] = w;
+  const double fyy = fy * c.y;
+  v[4] = fyy * c.r2; v[5] = fyy * c.r4; v[6] = fy * c.ay; v[7] = fy * 2.0 * c.xy; v[8] = fyy * c.r6;
+  const double b0 = fy * c.dxy * c.iz, b1 = fy * c.dyy * c.iz, b2 = -fma(b0, c.x, b1 * c.y);
+  huber_row_tail(c, b0, b1, b2, r * w, v);
+}
+
+// both residual components of an observation: fx xd + px - u, fy yd + py - v
+__device__ __forceinline__ void huber_residuals(const double* k, const ObsCommon& c, double u, double vm, double& ru, double& rv) {
+#pragma clang fp contract(off)
+  ru = fma(k[0], c.xd, k[2]) - u;
+  rv = fma(k[1], c.yd, k[3]) - vm;
+}
+
 // EXTENSION (cc_intrinsics_huber.hpp): ceres::HuberLoss(a) at s = |r|^2 -- rho and the row weight sqrt(rho') of the robust
 // sweeps. The tail in the form of the rig path's huber() (cc_rig.hip; a local copy, as rig_inner_huber is): |r| = s y and
 // sqrt(a / |r|) = q rsqrt(q), q = a y, from two refined reciprocal square roots. Both branches are computed and two values

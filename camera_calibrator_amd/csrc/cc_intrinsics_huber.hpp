@@ -29,70 +29,9 @@ namespace cc {
 // copy of the loop under another name gets other choices and blocks that differ in the last bits. With the choices written
 // down a weight of exactly 1 reproduces k_intr_sweep's rows bit for bit -- a threshold no observation exceeds leaves the
 // blocks what they are with the loss off (tests/test_gpu_intr_huber.py holds the two kernels together). Nothing here is left
-// to contract: every sum of a product is an fma.
+// to contract: every sum of a product is an fma. (The functions -- huber_obs_common, huber_row_u, huber_row_v, huber_residuals -- live in
+// cc_intrinsics_dev.hpp: the persistent kernel's two sweeps, full and residual-only, are written with them too.)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void huber_obs_common(const double* k, const double* R, const double* t,
-                                                 double X0, double X1, double X2, ObsCommon& c) {
-#pragma clang fp contract(off)
-  c.a0 = fma(R[2], X2, fma(R[1], X1, R[0] * X0));
-  c.a1 = fma(R[5], X2, fma(R[3], X0, R[4] * X1));
-  c.a2 = fma(R[8], X2, fma(R[6], X0, R[7] * X1));
-  const double xc = c.a0 + t[0], yc = c.a1 + t[1], zc = c.a2 + t[2];
-  c.iz = 1.0 / zc;
-  c.x = xc * c.iz;
-  c.y = yc * c.iz;
-  const double k1 = k[4], k2 = k[5], p1 = k[6], p2 = k[7], k3 = k[8];
-  const double xx = c.x * c.x, yy = c.y * c.y;
-  c.xy = c.x * c.y;
-  c.r2 = fma(c.y, c.y, xx);
-  c.r4 = c.r2 * c.r2;
-  c.r6 = c.r4 * c.r2;
-  const double m = fma(k3, c.r6, fma(k2, c.r4, fma(k1, c.r2, 1.0)));
-  c.ax = fma(2.0, xx, c.r2);
-  c.ay = fma(2.0, yy, c.r2);
-  c.xd = fma(p2, c.ax, fma(2.0 * p1, c.xy, c.x * m));
-  c.yd = fma(p1, c.ay, fma(2.0 * p2, c.xy, c.y * m));
-  const double mp2 = 2.0 * fma(3.0 * k3, c.r4, fma(2.0 * k2, c.r2, k1));
-  c.dxx = fma(6.0 * p2, c.x, fma(2.0 * p1, c.y, fma(mp2, xx, m)));
-  c.dxy = fma(2.0 * p2, c.y, fma(2.0 * p1, c.x, mp2 * c.xy));
-  c.dyy = fma(6.0 * p1, c.y, fma(2.0 * p2, c.x, fma(mp2, yy, m)));
-}
-
-// the pose columns and the residual behind a row's first nine entries: b0, b1 = d r / d (x, y) / z, b2 the z column
-__device__ __forceinline__ void huber_row_tail(const ObsCommon& c, double b0, double b1, double b2, double rw, double* v) {
-#pragma clang fp contract(off)
-  v[9] = 2.0 * fma(b2, c.a1, -(b1 * c.a2)); v[10] = 2.0 * fma(b0, c.a2, -(b2 * c.a0)); v[11] = 2.0 * fma(b1, c.a0, -(b0 * c.a1));
-  v[12] = b0; v[13] = b1; v[14] = b2; v[15] = rw;
-}
-
-// row_u / row_v with the residual r handed in (huber_residuals) and the weight w on the row's factors, as there
-__device__ __forceinline__ void huber_row_u(const double* k, const ObsCommon& c, double r, double* v, double w) {
-#pragma clang fp contract(off)
-  const double fx = k[0] * w;
-  v[0] = c.xd * w; v[1] = 0.0; v[2] = w; v[3] = 0.0;
-  const double fxx = fx * c.x;
-  v[4] = fxx * c.r2; v[5] = fxx * c.r4; v[6] = fx * 2.0 * c.xy; v[7] = fx * c.ax; v[8] = fxx * c.r6;
-  const double b0 = fx * c.dxx * c.iz, b1 = fx * c.dxy * c.iz, b2 = -fma(b1, c.y, b0 * c.x);
-  huber_row_tail(c, b0, b1, b2, r * w, v);
-}
-
-__device__ __forceinline__ void huber_row_v(const double* k, const ObsCommon& c, double r, double* v, double w) {
-#pragma clang fp contract(off)
-  const double fy = k[1] * w;
-  v[0] = 0.0; v[1] = c.yd * w; v[2] = 0.0; v[3] = w;
-  const double fyy = fy * c.y;
-  v[4] = fyy * c.r2; v[5] = fyy * c.r4; v[6] = fy * c.ay; v[7] = fy * 2.0 * c.xy; v[8] = fyy * c.r6;
-  const double b0 = fy * c.dxy * c.iz, b1 = fy * c.dyy * c.iz, b2 = -fma(b0, c.x, b1 * c.y);
-  huber_row_tail(c, b0, b1, b2, r * w, v);
-}
-
-// both residual components of an observation: fx xd + px - u, fy yd + py - v
-__device__ __forceinline__ void huber_residuals(const double* k, const ObsCommon& c, double u, double vm, double& ru, double& rv) {
-#pragma clang fp contract(off)
-  ru = fma(k[0], c.xd, k[2]) - u;
-  rv = fma(k[1], c.yd, k[3]) - vm;
-}
-
 // ---------------------------------------------------------------------------------------------
 // robust sweep: k_intr_sweep with the Huber weight on the rows and 1/2 sum rho as the cost (huber_a > 0).
 // sm layout and flags as in k_intr_sweep; sm[176..179] the waves' cost sums.

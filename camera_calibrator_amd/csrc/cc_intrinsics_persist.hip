@@ -19,6 +19,11 @@
 //             statistics rows, takes the decision (lm_init / lm_decide), broadcasts {done, cur, radius (, Jacobi
 //             scales)}. Seam 2: gathers the eighty totals of the column owners, gradient / radius tests, 9 x 9 reduced solve with
 //             the matrix distributed by rows over nine lanes (v_readlane pivots), broadcasts {done, valid, step}.
+// The LAST sweep of a solve is residual-only: a decision that ends the solve reads the four statistics and nothing else of its
+// round, so where the control predicts such a decision (iteration limit, or function tolerance from the last two accepted cost
+// changes: persist_predicts_end; bit 32 of the step's broadcast) the workers evaluate the residuals alone and form the cost with
+// packed matrix products (cc_persist_pack.hpp: the bits of the full sweep). A prediction that turns out wrong goes the miss route, the
+// workers sweeping the accepted candidate again in full: results never depend on it (cc_intrinsics_set_final_sweep).
 // Seams are self-validating 8-byte words {epoch32 : half of a double}, stored and polled with agent-scope (sc1)
 // accesses: an aligned 8-byte store is single-copy atomic, so there is no flag, no fence, no drain (MI355X guide,
 // Guideline 16 R2). Sums over rows run in a fixed order: results do not depend on timing or placement. Every wait is
@@ -27,6 +32,7 @@
 // everybody leaves, and a handle alone on its device runs the solve again with two kernels per iteration.
 #include "cc_intrinsics_persist.hpp"
 #include "cc_persist_dev.hpp"
+#include "cc_persist_pack.hpp"
 #include "cc_persist_publish.hpp"
 #include "cc_persist_sum.hpp"
 
@@ -44,7 +50,8 @@ enum { TM_Y = 0, TM_POSE = 60, TM_SP = 76, TM_STEP = 84, TM_R = 100, TM_T = 109,
        TM_QW = 124, TM_STAT = 128 /* cost, q_model, step^2, |x|^2, then nine diagonal entries (first round) */ };
 // workgroup scratch (doubles)
 enum { WG_INTR = 0 /* [2][16] */, WG_X = 64 /* the control's last broadcast: flags, radius, nine doubles */, WG_DS = 66 /* ... the step */,
-       WG_SS = 80 /* scales of the shared columns as the workers see them: 1 */, WG_R0 = 96 /* initial radius */, WG_OPT = 100 /* jacobi, min / max LM diagonal, max radius */,
+       WG_SS = 80 /* scales of the shared columns as the workers see them: 1 */, WG_R0 = 96 /* initial radius */,
+       WG_RO = 97 /* the residuals of each of the workgroup's frames fit its team's staging tiles */, WG_OPT = 100 /* jacobi, min / max LM diagonal, max radius */,
        WG_TAB = 104 /* pj / pk byte tables */,
        // slot table of the elimination row (80 slots; built once per solve; no scale factors: the control scales the sums):
        // source entry of the Gram block, the two columns of Z whose product is subtracted (| 1 << 16: there is one)
@@ -53,7 +60,7 @@ enum { WG_INTR = 0 /* [2][16] */, WG_X = 64 /* the control's last broadcast: fla
 static_assert(TM_POSE - TM_Y >= 6 * 10 && TM_SP - TM_POSE >= 2 * 8 && TM_STEP - TM_SP >= 6 && TM_R - TM_STEP >= 15 && TM_T - TM_R >= 9 && TM_KC - TM_T >= 3 &&
               TM_STEP2 - TM_KC >= 9 && TM_QW - TM_XN2 >= 1 && TM_STAT - TM_QW >= 4 && TM_STAT + 4 + 9 <= 192,
               "per-team scratch: Y (6 x 10), two poses, pose scale, step (9 + 6), R, t, intrinsics, scalars, statistics row -- inside the 192 doubles persist_lds_doubles gives a team");
-static_assert(WG_X - WG_INTR >= 2 * 16 && WG_DS - WG_X >= 2 && WG_SS - WG_DS >= 9 && WG_R0 - WG_SS >= 9 && WG_OPT - WG_R0 >= 1 && WG_TAB - WG_OPT >= 4 &&
+static_assert(WG_X - WG_INTR >= 2 * 16 && WG_DS - WG_X >= 2 && WG_SS - WG_DS >= 9 && WG_R0 - WG_SS >= 9 && WG_RO - WG_R0 >= 1 && WG_OPT - WG_RO >= 1 && WG_TAB - WG_OPT >= 4 &&
               WG_TZ - WG_TGI >= 80 / 2 && WG_TZ + 80 / 2 <= 512,
               "workgroup scratch: both intrinsics, broadcast (2 + 9), scales, options, tables of the 80-slot row -- inside the 512 doubles of persist_lds_doubles");
 
@@ -271,8 +278,11 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
   LmCtl* s_ctl = reinterpret_cast<LmCtl*>(lds + 1232);         // 18 doubles
   LmOpts* s_opts = reinterpret_cast<LmOpts*>(lds + 1252);      // 12 doubles
   cc_iteration* s_log = reinterpret_cast<cc_iteration*>(lds + 1264);
-  int* s_int = reinterpret_cast<int*>(lds + 1296);             // [0] gather ok, [1] a record was logged this round
+  int* s_int = reinterpret_cast<int*>(lds + 1296);             // [0] gather ok, [1] a record was logged this round, [2] the workers' assumption held,
+                                                               // [3] the NEXT decision is predicted to end the solve (the workers sweep residuals only),
+                                                               // [5] a prediction was wrong: no more of them, [6] residual-only rounds, [7] ... redone
   u64* s_seq = reinterpret_cast<u64*>(lds + 1300);             // the sequence number this solve is published under
+  double* s_ccprev = lds + 1301;                               // cost change of the last accepted decision of this launch (0: none)
   const int tid = threadIdx.x, wave = tid >> 6;
   static_assert(sizeof(cc_iteration) <= 32 * 8, "log record scratch");
   // initial state: a fresh control block (every launch is a whole solve), options, intrinsics of the starting point
@@ -283,7 +293,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
   if (tid == 48 && P.host_pub) *s_seq = *P.pub_seq + 1ull;
   __syncthreads();
   if (tid < 9) s_intr[tid] = (Q.restart ? P.init_intr : P.intr)[tid];
-  if (tid == 0) s_int[1] = 0;
+  if (tid == 0) { s_int[1] = 0; s_int[3] = 0; s_int[5] = 0; s_int[6] = 0; s_int[7] = 0; *s_ccprev = 0.0; }
   __syncthreads();
   // (a reference into LDS, not a copy: twelve doubles alive across the round loop were spilled in the 128-register build of
   // four teams, and reloaded one by one inside the reduced solve)
@@ -319,6 +329,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
     if (tid == 0) {
       LmCtl c = *s_ctl;
       const int len0 = c.log_len, prev_cur = c.cur & 1, was_valid = c.step_valid;
+      const int ro_now = s_int[3];   // the workers swept this round's candidate residual-only: no Gram block, no elimination row of theirs
       const double prev_radius = c.radius;
       const double* kc0 = s_intr + (c.cur ? 16 : 0);   // accepted intrinsics
       const double* kc1 = s_intr + (c.cur ? 0 : 16);   // candidate
@@ -354,8 +365,27 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       *s_ctl = c;
       s_int[1] = c.log_len != len0;
       // did the workers' assumption hold? (the same expression they evaluate: persist_spec_radius)
+      // (never after a residual-only sweep: a decision that does not end the solve then goes the miss route, whatever it says)
       s_int[2] = phase0 ? (!c.done && c.radius == o.initial_radius)
-                        : (was_valid && !c.done && (c.cur & 1) == (prev_cur ^ 1) && c.radius == persist_spec_radius(prev_radius, o.max_radius));
+                        : (!ro_now && was_valid && !c.done && (c.cur & 1) == (prev_cur ^ 1) && c.radius == persist_spec_radius(prev_radius, o.max_radius));
+      // ---- will the NEXT decision end the solve? Then its sweep need not build a Gram block nobody reads (cc_intrinsics_persist.hpp).
+      // Predicted where a point is accepted (the starting point: by the iteration limit alone) and the solve goes on: the iteration
+      // limit (certain), or the function tolerance from the last two accepted cost changes. Off as a rank of an exchange.
+      const bool accepted = !phase0 && (c.cur & 1) != prev_cur;
+      if (ro_now) {
+        s_int[6]++;
+        if (!c.done) {
+          if (Q.final_sweep == 1) s_int[5] = 1;
+          if (accepted) s_int[7]++;   // (the workers sweep the accepted candidate again, in full)
+        }
+      }
+      int pred = 0;
+      if (!c.done && s_int[0] && Q.final_sweep != 0 && !s_int[5] && !P.x.on && (phase0 || accepted)) {
+        const double cc_k = phase0 ? 0.0 : s_log->cost_change;
+        pred = Q.final_sweep == 2 || c.iter + 1 >= o.max_iterations || persist_predicts_end(cc_k, *s_ccprev, o.function_tolerance, c.x_cost);
+      }
+      if (accepted) *s_ccprev = s_log->cost_change;
+      s_int[3] = pred;
       s_bc[0] = (double)((c.done ? 1 : 0) | ((c.cur & 1) << 3));
       s_bc[1] = c.radius;
 #pragma unroll
@@ -363,6 +393,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
     }
     __syncthreads();
     const bool hit = s_int[2] != 0;
+    const int pred_flag = s_int[3] ? 32 : 0;   // (rides in the step's broadcast)
     if (s_ctl->done || !hit) {
       if (tid < 22) ag_st(Q.xbox + tid, granule(e2, s_bc[tid >> 1], tid & 1));
       if (s_ctl->done) break;   // (a decision that ends the solve -- tolerance, iteration limit -- still owes its log record: behind the publication)
@@ -452,7 +483,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
       if (lane == 0) {
         // the flags first (they are what the broadcast waits for), the control block and the log record behind them:
         // lm_finalize below sets `done` exactly when `go` is false
-        s_bc[0] = (double)((go ? 0 : 1) | (go && ok ? 2 : 0) | (hit ? 4 : 0) | (cur << 3));
+        s_bc[0] = (double)((go ? 0 : 1) | (go && ok ? 2 : 0) | (hit ? 4 : 0) | (cur << 3) | pred_flag);
         s_bc[1] = radius;
         s_bc[12] = gmax;   // (for thread 0's bookkeeping below: not part of the broadcast)
       }
@@ -514,6 +545,7 @@ __device__ __forceinline__ void persist_control(const IntrDev& P, const PersistD
   }
   if (lane < 32 && failed == 0u) P.intr[lane] = intr_l;
   if (owes_record && lane < kLogWords) reinterpret_cast<u64*>(P.log + (log_len - 1))[lane] = log_l;
+  if (lane < 2) Q.fs_counts[lane] = (unsigned)s_int[6 + lane];   // (cc_intrinsics_final_sweep_counts)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -574,6 +606,14 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     for (int j = 0; j < 9; ++j)
       for (int k = j; k < 9; ++k) { pj[oo] = (unsigned char)j; pk[oo] = (unsigned char)k; ++oo; }
   }
+  if (tid == 34) {
+    bool fits = true;
+    for (int k = 0; k < TEAMS; ++k) {
+      const int64_t fk = (int64_t)blockIdx.x * TEAMS + k;
+      if (fk < P.F && P.off[fk + 1] - P.off[fk] > (int64_t)kPackMaxPasses * kSweepThreads) fits = false;
+    }
+    s_wg[WG_RO] = fits ? 1.0 : 0.0;
+  }
   if (tid >= 64 && tid < 64 + 16) s_wg[WG_X + tid - 64] = 0.0;
   // The Jacobi scales of the NINE SHARED columns never reach the workers (they are sums over all frames, known to the
   // control after the first statistics): a worker eliminates with unit scales there -- the control scales the sums it
@@ -621,13 +661,16 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
   int cur = 0;
   double radius = 1.0;   // trust-region radius of the accepted point (known from the first broadcast on)
   bool step_valid = true, failed = false;
+  bool ends_next = false;   // the control predicts that this round's decision ends the solve (bit 32 of the step's broadcast)
   for (int round = 0; round < Q.max_rounds; ++round) {
     const unsigned e1 = Q.epoch0 + 3u * (unsigned)round + 1u, e2 = e1 + 1u, e3 = e1 + 2u;
     const bool phase0 = round == 0;
     const bool do_sweep = phase0 || step_valid;
     const int dst = phase0 ? cur : (cur ^ 1);
+    // A decision that ends the solve reads the four statistics and nothing else: the sweep of such a round evaluates the residuals
+    // only -- no Gram block, no elimination on the assumption (the control then never reports that it held). Workgroup-uniform.
+    const bool resid_only = ends_next && do_sweep && __builtin_amdgcn_readfirstlane((int)s_wg[WG_RO]) != 0;
     // =========================== sweep (candidate point, or the starting point in the first round)
-    d4 acc0, acc1;
     if (do_sweep) {
       CC_FRESH_TID(tid);
       const int ttid = tid & 255, lane = tid & 63;
@@ -693,6 +736,14 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
         const double qw = wave_sum(qterm);
         if (lane == 0) sm[TM_QW + twave] = qw;
       }
+    }
+    // ---- the full sweep of the point in LDS (TM_R, TM_T, TM_KC) into Gram block `dst`: main loop, cross-wave reduction, and
+    // (with_stats) the statistics of the frame. Called a second time in a round whose residual-only sweep was not the solve's last.
+    auto full_sweep = [&](const bool with_stats) {
+    d4 acc0, acc1;
+    {
+      CC_FRESH_TID(tid);
+      const int ttid = tid & 255, lane = tid & 63;
       double R[9], tt[3], kk[9];
 #pragma unroll
       for (int i = 0; i < 9; ++i) R[i] = rfl(sm[TM_R + i]);
@@ -706,6 +757,74 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
       acc1 = d4{0.0, 0.0, 0.0, 0.0};
       // (Waves that share a SIMD -- one per team -- enter the loop in lockstep. A start staggered by k sleep units per team, so that one
       // team's LDS staging falls under another's matrix products, was measured at several k and never paid: removed in round 6.)
+      // (a wave without observations never reads its prefetch: said here, so that five registers are not held round the loop for it)
+      if (npass == 0) { nm = float2{0.f, 0.f}; nX0 = nX1 = nX2 = 0.f; }
+      for (int p = 0; p < npass; ++p) {
+        const int64_t idx = s0 + (int64_t)p * kSweepThreads + ttid;
+        const bool valid = idx < s1;
+        const float2 m = nm;
+        const float X0 = nX0, X1 = nX1, X2 = nX2;
+        {   // next pass -- after the last one, the first pass of the next round -- unconditionally
+          const int64_t nidx = p + 1 < npass ? idx + kSweepThreads : s0 + ttid;
+          const int64_t ic = nidx < s1 ? nidx : safe0;
+          nm = uv2[ic];
+          nX0 = P.xyz[ic * 3]; nX1 = P.xyz[ic * 3 + 1]; nX2 = P.xyz[ic * 3 + 2];
+        }
+        // (the model with its fused multiply-adds spelled out -- the compiler's own choices differ between the copies of this loop and
+        // from the residual-only loop, in the last bits; written down, all of them compute what k_intr_sweep computes)
+        ObsCommon oc;
+        huber_obs_common<TEAMS == 1>(kk, R, tt, (double)X0, (double)X1, (double)X2, oc);
+        double v[16], ru, rv;
+        const double wrow = valid ? 1.0 : 0.0;   // (an idle lane's rows are zero: the weight rides on the rows' factors)
+        huber_residuals(kk, oc, (double)m.x, (double)m.y, ru, rv);
+        huber_row_u(kk, oc, ru, v, wrow);
+        stage_row(stage, lane, v);
+        wave_lds_fence();
+        gram_rows_ahead(stage, lane, acc0, acc1);
+        wave_lds_fence();
+        huber_row_v(kk, oc, rv, v, wrow);
+        stage_row(stage, lane, v);
+        wave_lds_fence();
+        gram_rows_ahead(stage, lane, acc0, acc1);
+        wave_lds_fence();
+      }
+      // ---- cross-wave reduction of the 16 x 16 block into the frame's LDS slot
+      __syncthreads();   // s_blk aliases the staging tiles
+    }
+    {
+      CC_FRESH_TID(tid);
+      const int ttid = tid & 255, lane = tid & 63;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s_blk[twave * 256 + ((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc0[r] + acc1[r];
+      __syncthreads();
+      const double g = gram_entry_held(mask, ttid) ? 0.0 : (s_blk[ttid] + s_blk[256 + ttid]) + (s_blk[512 + ttid] + s_blk[768 + ttid]);   // (constant coordinates: zero rows and columns)
+      s_G[(team * 2 + dst) * 256 + ttid] = g;
+      if (with_stats && ttid == 255) {
+        sm[TM_STAT + ST_COST] = 0.5 * g;
+        sm[TM_STAT + ST_QMODEL] = (sm[TM_QW] + sm[TM_QW + 1]) + (sm[TM_QW + 2] + sm[TM_QW + 3]);
+        sm[TM_STAT + ST_STEP2] = sm[TM_STEP2];
+        sm[TM_STAT + ST_XNORM2] = sm[TM_XN2];
+      }
+      if (with_stats && phase0 && ttid < 9 * 17 && ttid % 17 == 0) sm[TM_STAT + 4 + ttid / 17] = g;
+      __syncthreads();
+    }
+    };
+    // ---- the residual-only sweep: the main loop's observations, prefetch and residual expressions (huber_obs_common: the compiler's
+    // fused multiply-adds of the full loop, spelled out), two doubles per lane and pass into the team's staging tiles instead of
+    // two rows of sixteen. The cost keeps the bits of the full sweep because it is still formed in the matrix unit, product for
+    // product: one wave of the team -- wave `team`, as for the other serial pieces -- advances the team's eight chains together
+    // (cc_persist_pack.hpp) and adds the eight diagonal entries in the order of the full sweep's reduction.
+    auto resid_sweep = [&]() {
+    {
+      CC_FRESH_TID(tid);
+      const int ttid = tid & 255, lane = tid & 63;
+      double R[9], tt[3], kk[9];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) R[i] = rfl(sm[TM_R + i]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) tt[i] = rfl(sm[TM_T + i]);
+#pragma unroll
+      for (int i = 0; i < 9; ++i) kk[i] = rfl(sm[TM_KC + i]);
       for (int p = 0; p < npass; ++p) {
         const int64_t idx = s0 + (int64_t)p * kSweepThreads + ttid;
         const bool valid = idx < s1;
@@ -718,39 +837,54 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
           nX0 = P.xyz[ic * 3]; nX1 = P.xyz[ic * 3 + 1]; nX2 = P.xyz[ic * 3 + 2];
         }
         ObsCommon oc;
-        obs_common(kk, R, tt, (double)X0, (double)X1, (double)X2, oc);
-        double v[16];
-        const double wrow = valid ? 1.0 : 0.0;   // (an idle lane's rows are zero: the weight rides on the rows' factors)
-        row_u(kk, oc, (double)m.x, v, wrow);
-        stage_row(stage, lane, v);
-        wave_lds_fence();
-        gram_rows_ahead(stage, lane, acc0, acc1);
-        wave_lds_fence();
-        row_v(kk, oc, (double)m.y, v, wrow);
-        stage_row(stage, lane, v);
-        wave_lds_fence();
-        gram_rows_ahead(stage, lane, acc0, acc1);
-        wave_lds_fence();
+        huber_obs_common<TEAMS == 1>(kk, R, tt, (double)X0, (double)X1, (double)X2, oc);
+        double ru, rv;
+        huber_residuals(kk, oc, (double)m.x, (double)m.y, ru, rv);
+        const double wrow = valid ? 1.0 : 0.0;
+        tstage[pack_write_slot(twave, p, 0, lane)] = ru * wrow;
+        tstage[pack_write_slot(twave, p, 1, lane)] = rv * wrow;
       }
-      // ---- cross-wave reduction of the 16 x 16 block into the frame's LDS slot
-      __syncthreads();   // s_blk aliases the staging tiles
+      __syncthreads();
     }
-    if (do_sweep) {
+    {
       CC_FRESH_TID(tid);
-      const int ttid = tid & 255, lane = tid & 63;
+      const int lane = tid & 63;
+      if (has_frame && twave == (team & 3)) {
+        // steps of this lane's chain (its wave's passes) and of the team's longest (wave 0's)
+        const int64_t n = s1 - s0, wr = n - (int64_t)(pack_read_chain(lane) >> 1) * 64;
+        const int mine = pack_read_chain(lane) < kPackChains && wr > 0 ? pack_chain_steps((int)((wr + kSweepThreads - 1) / kSweepThreads)) : 0;
+        const int steps = pack_chain_steps((int)((n + kSweepThreads - 1) / kSweepThreads));
+        d4 acc = d4{0.0, 0.0, 0.0, 0.0};
+        for (int s0_ = 0; s0_ < steps; s0_ += kPackStepsPerPass) {
+          double a[kPackStepsPerPass];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) s_blk[twave * 256 + ((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc0[r] + acc1[r];
-      __syncthreads();
-      const double g = gram_entry_held(mask, ttid) ? 0.0 : (s_blk[ttid] + s_blk[256 + ttid]) + (s_blk[512 + ttid] + s_blk[768 + ttid]);   // (constant coordinates: zero rows and columns)
-      s_G[(team * 2 + dst) * 256 + ttid] = g;
-      if (ttid == 255) {
-        sm[TM_STAT + ST_COST] = 0.5 * g;
-        sm[TM_STAT + ST_QMODEL] = (sm[TM_QW] + sm[TM_QW + 1]) + (sm[TM_QW + 2] + sm[TM_QW + 3]);
-        sm[TM_STAT + ST_STEP2] = sm[TM_STEP2];
-        sm[TM_STAT + ST_XNORM2] = sm[TM_XN2];
+          for (int u = 0; u < kPackStepsPerPass; ++u) {
+            const double v = tstage[pack_read_slot(s0_ + u, lane)];
+            a[u] = s0_ + u < mine ? v : 0.0;
+          }
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int u = 0; u < kPackStepsPerPass; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], a[u], acc, 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        double c[4];
+#pragma unroll
+        for (int w = 0; w < 4; ++w)   // acc0 + acc1 of wave w
+          c[w] = lane_bcast(acc[pack_diag_reg(2 * w)], pack_diag_lane(2 * w)) + lane_bcast(acc[pack_diag_reg(2 * w + 1)], pack_diag_lane(2 * w + 1));
+        const double g = (c[0] + c[1]) + (c[2] + c[3]);
+        if (lane == 0) {
+          sm[TM_STAT + ST_COST] = 0.5 * g;
+          sm[TM_STAT + ST_QMODEL] = (sm[TM_QW] + sm[TM_QW + 1]) + (sm[TM_QW + 2] + sm[TM_QW + 3]);
+          sm[TM_STAT + ST_STEP2] = sm[TM_STEP2];
+          sm[TM_STAT + ST_XNORM2] = sm[TM_XN2];
+        }
       }
-      if (phase0 && ttid < 9 * 17 && ttid % 17 == 0) sm[TM_STAT + 4 + ttid / 17] = g;
       __syncthreads();
+    }
+    };
+    if (do_sweep) {
+      if (resid_only) resid_sweep();
+      else full_sweep(true);
     }
     // ---- statistics row of the workgroup (teams in order) -> control
     {
@@ -918,12 +1052,16 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     // ---- column `c` of the G rows is added up by its OWNER, worker c mod G (it would only be waiting for the step otherwise),
     // on wave 3: idle here in every form, and polling from the moment the workgroup's own row has been issued
     if (wave == 3 && (int)blockIdx.x < kPartialCols)
-      own_columns<THREADS / kPartialCols>(box, Q.lbox, Q.G, (int)blockIdx.x, tag, s_stage + 2048, Q.fail, tid0, (phase0 ? Q.first_shift : Q.timeout_shift));
+      own_columns<THREADS / kPartialCols>(box, Q.lbox, Q.G, (int)blockIdx.x, tag, s_stage + 2048, Q.fail, tid_e, (phase0 ? Q.first_shift : Q.timeout_shift));
     };
     // one wave waits for the control's broadcast `tag` (flags, radius, nine doubles) -> s_wg[WG_X ..]
     auto wait_bcast = [&](const unsigned tag) {
       CC_FRESH_TID(tid);
-      if (wave == 0 && !bcast_wait(Q.xbox, tag, 11, s_wg + WG_X, Q.fail, tid & 63, (phase0 ? Q.first_shift : Q.timeout_shift))) s_wg[WG_X] = 17.0;   // done + failed
+      if (wave == 0 && !bcast_wait(Q.xbox, tag, 11, s_wg + WG_X, Q.fail, tid & 63, (phase0 ? Q.first_shift : Q.timeout_shift))) {
+        int gave_up = 17;   // done + failed (formed here: as a literal the double is parked in a register pair across the round loop)
+        asm volatile("" : "+s"(gave_up));
+        s_wg[WG_X] = (double)gave_up;
+      }
       __syncthreads();
     };
 
@@ -931,29 +1069,36 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     // Eliminating NOW, next to the control's gathering and deciding, takes a seam out of the round when it holds.
     // (first round: the starting point is "accepted" at the initial radius unless the solve ends before it begins; its
     // elimination also computes the frame's Jacobi scale)
-    const bool spec = do_sweep;
+    // (not in a round predicted to be the last: its elimination row would not be read -- whether the sweep was residual-only or, in
+    // a workgroup with a frame too long for that, full)
+    const bool spec = do_sweep && !ends_next;
     const double radius_spec = phase0 ? s_wg[WG_R0] : persist_spec_radius(radius, s_wg[WG_OPT + 3]);
     if (spec) eliminate_and_post(dst, radius_spec, phase0, Q.pbox, e2);
     wait_bcast(e2);
-    int fl = (int)s_wg[WG_X];
+    int fl = __builtin_amdgcn_readfirstlane((int)s_wg[WG_X]);   // (the flags, and what is derived from them, in scalar registers)
     if (fl & 16) failed = true;
     if (fl & 1) { cur = (fl >> 3) & 1; break; }
     if (fl & 4) {   // the assumption held: this broadcast IS the step
       cur = dst;
-      radius = radius_spec;
+      radius = rfl(radius_spec);   // (wave-uniform: in scalar registers across the next sweep)
     } else {        // it did not (or there was none): eliminate with what the decision says, then wait for the step
       cur = (fl >> 3) & 1;
-      radius = s_wg[WG_X + 1];
+      radius = rfl(s_wg[WG_X + 1]);
+      // (the prediction was wrong and the candidate is accepted: its Gram block is now needed -- pose, rotation and intrinsics of the
+      // candidate are still in LDS, the statistics have gone out)
+      if (resid_only && cur == dst) full_sweep(false);
       eliminate_and_post(cur, radius, false, Q.rbox, e3);   // (never the first round: that one always holds or ends the solve)
       wait_bcast(e3);
-      fl = (int)s_wg[WG_X];
+      fl = __builtin_amdgcn_readfirstlane((int)s_wg[WG_X]);
       if (fl & 16) failed = true;
       if (fl & 1) { cur = (fl >> 3) & 1; break; }
     }
     step_valid = (fl & 2) != 0;
+    ends_next = (fl & 32) != 0;
   }
   // ---- the solve is over: the frame's accepted pose goes back to HBM (cc_intrinsics_get_state, the next solve)
-  if (!failed && ag_ld32(Q.fail) == 0u && has_frame && (tid0 & 255) < 7) P.pose[((size_t)cur * P.F + f) * 8 + (tid0 & 255)] = sm[TM_POSE + cur * 8 + (tid0 & 255)];
+  CC_FRESH_TID(tid_w);   // (as in the round loop: the index is formed here, not held across it)
+  if (!failed && ag_ld32(Q.fail) == 0u && has_frame && (tid_w & 255) < 7) P.pose[((size_t)cur * P.F + f) * 8 + (tid_w & 255)] = sm[TM_POSE + cur * 8 + (tid_w & 255)];
   asm volatile("" ::"v"(nm.x), "v"(nX0), "v"(nX1), "v"(nX2));   // (the last prefetch has no consumer)
 }
 

@@ -30,7 +30,19 @@ struct PersistDev {
   int32_t first_shift;        // ... and the waits of the FIRST round: 20 (10.5 ms) alone on the device -- a first round that has not
                               // come together by then (every workgroup started, one sweep of at most ~0.1 ms) never will, and the
                               // caller gets its rerun in the two-kernel form after 10 ms instead of 1.3 s; with peer ranks as above
+  int32_t final_sweep;        // cc_intrinsics_set_final_sweep: 0 every sweep full, 1 the sweep of a round whose decision is predicted to end
+                              // the solve evaluates residuals only, 2 (tests) every accepting decision predicts the end
+  unsigned* fs_counts;        // [2] of the last solve: rounds swept residual-only, and those of them whose full sweep was redone
 };
+
+// The control's prediction, made at a decision that accepts a step with cost change cc_k > 0 behind an accepted one with cc_prev > 0:
+// will the NEXT decision end the solve by function tolerance? The changes of a converging solve shrink at least geometrically, so
+// the next one is taken as cc_k * min(1, cc_k / cc_prev) and held against the tolerance's own limit at the new accepted cost.
+inline __host__ __device__ bool persist_predicts_end(double cc_k, double cc_prev, double function_tolerance, double x_cost) {
+  if (!(cc_k > 0.0) || !(cc_prev > 0.0)) return false;
+  const double ratio = cc_k / cc_prev;
+  return cc_k * (ratio < 1.0 ? ratio : 1.0) <= function_tolerance * x_cost;
+}
 
 // workgroups of the `teams`-frame variant that can be resident on `device` at once (occupancy query x CUs)
 int persist_resident_workgroups(int device, int teams, int* out);

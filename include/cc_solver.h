@@ -273,6 +273,15 @@ int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks
  * cc_intrinsics_exchange_export / _attach, cc_intrinsics_comm_init and cc_intrinsics_profile_solve return CC_ERR_STATE on a
  * handle with the loss on. */
 int cc_intrinsics_set_huber(cc_intrinsics* h, double a_pixels);
+/* The sweep of the LAST round of a solve in the persistent form. A decision that ends a solve reads the candidate's cost and
+ * nothing else of its sweep; where the control predicts such a decision (iteration limit: certain; function tolerance: from the
+ * last two accepted cost changes) the workers evaluate residuals only, and sweep again in full should the solve go on.
+ * mode 0: every sweep full; 1: as described (the default); 2: predicted at every accepting decision (tests). The results are
+ * the same bits in every mode. Other values: CC_ERR_BAD_ARGUMENT. */
+int cc_intrinsics_set_final_sweep(cc_intrinsics* h, int32_t mode);
+/* Of the last persistent solve of the handle: rounds swept residual-only, and how many of those were swept again in full. Waits
+ * for the handle's stream. Zeros before the first such solve; a solve in the two-kernel form leaves them alone. */
+int cc_intrinsics_final_sweep_counts(cc_intrinsics* h, int32_t* residual_only, int32_t* redone);
 /* obs_cost [N]: the cost of every observation at the current point, in the caller's order -- 1/2 rho(s) with the loss on,
  * 1/2 s with it off. */
 int cc_intrinsics_obs_cost(cc_intrinsics* h, double* obs_cost);
