@@ -1,6 +1,7 @@
 // cc_device.hpp -- device helpers shared by the intrinsics and the rig kernels (gfx950).
 #pragma once
 #include "cc_common.hpp"
+#include "cc_gram_blocks.hpp"
 
 namespace cc {
 
@@ -171,6 +172,77 @@ __device__ __forceinline__ void gram_rows_ahead(const double* stage, int lane, d
   __builtin_amdgcn_sched_barrier(0);
   gram_products(a, acc0, acc1);
   __builtin_amdgcn_sched_barrier(0);
+}
+
+// The same contraction on ten 4 x 4 blocks of the 16 x 16 block, one of every transposed pair (cc_gram_blocks.hpp: operands,
+// products and what every accumulator lane holds): six operand reads and five 4 x 4 x 4 (four blocks) products per PAIR of row sets,
+// the pair's first set into chain 0, its second into chain 1 -- the row sets and the order of gram_products' acc0 and acc1. Five
+// accumulator registers.
+struct GramBlocks { double c[kGbProducts]; };
+// pairs whose operands are read ahead of their products: 12 operand doubles (gram_rows_ahead: 16). Four pairs put k_intr_persist<2>
+// above its register budget (tests/test_persist_pack_cpu.py) and are no faster (profiles/r23/microbench_f64.txt).
+constexpr int kGbBatchPairs = 2;
+
+__device__ __forceinline__ void gram_blocks_clear(GramBlocks& g) {
+#pragma unroll
+  for (int n = 0; n < kGbProducts; ++n) g.c[n] = 0.0;
+}
+// (a pair on is eight rows on: the swizzle term r & 7 and with it the lane's six offsets are those of pair 0, the pair an immediate)
+template <int PAIR0, int NP>
+__device__ __forceinline__ void gram_block_operands(const double* stage, int lane, double* a) {
+  int base[kGbOperands];
+#pragma unroll
+  for (int o = 0; o < kGbOperands; ++o) {
+    const int r = gb_op_row(o, 0, lane), c = gb_op_comp(o, lane);
+    base[o] = r * 16 + (((c >> 1) ^ (r & 7)) << 1) + (c & 1);
+  }
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int o = 0; o < kGbOperands; ++o) a[p * kGbOperands + o] = stage[base[o] + (PAIR0 + p) * kGbPairRows * 16];
+}
+template <int N>
+__device__ __forceinline__ void gram_block_product(const double* a, GramBlocks& g) {
+  g.c[N] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[gb_prod_a(N)], a[gb_prod_b(N)], g.c[N], 0, 0, 0);
+}
+template <int NP>
+__device__ __forceinline__ void gram_block_products(const double* a, GramBlocks& g) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    gram_block_product<0>(a + p * kGbOperands, g);
+    gram_block_product<1>(a + p * kGbOperands, g);
+    gram_block_product<2>(a + p * kGbOperands, g);
+    gram_block_product<3>(a + p * kGbOperands, g);
+    gram_block_product<4>(a + p * kGbOperands, g);
+  }
+}
+// gram_rows_ahead's pinned schedule, a batch of NP pairs at a time: the batch's operand reads, then its products.
+template <int NP, int PAIR0 = 0>
+__device__ __forceinline__ void gram_blocks_ahead(const double* stage, int lane, GramBlocks& g) {
+  static_assert(kGbPairs % NP == 0, "whole batches");
+  if constexpr (PAIR0 < kGbPairs) {
+    double a[NP * kGbOperands];
+    gram_block_operands<PAIR0, NP>(stage, lane, a);
+    __builtin_amdgcn_sched_barrier(0);
+    gram_block_products<NP>(a, g);
+    __builtin_amdgcn_sched_barrier(0);
+    gram_blocks_ahead<NP, PAIR0 + NP>(stage, lane, g);
+  }
+}
+// A wave's two chains added (chain 0 + chain 1) and scattered into its 16 x 16 block `blk` (row-major), both triangles.
+__device__ __forceinline__ void gram_blocks_store(const GramBlocks& g, int lane, double* blk) {
+  blk[gb_acc_row(0, lane) * 16 + gb_acc_col(0, lane)] = g.c[0] + g.c[1];
+  {
+    const double s = g.c[2] + g.c[3];
+    const int r = gb_acc_row(2, lane), c = gb_acc_col(2, lane);
+    blk[r * 16 + c] = s;
+    blk[c * 16 + r] = s;
+  }
+  {
+    const double s = g.c[4] + dpp_f64<0x128>(g.c[4]);   // row_ror:8 -- the lane eight on (gb_partner_lane)
+    const int r = gb_acc_row(4, lane), c = gb_acc_col(4, lane);
+    blk[gb_store_mirrored(lane) ? c * 16 + r : r * 16 + c] = s;
+  }
 }
 
 

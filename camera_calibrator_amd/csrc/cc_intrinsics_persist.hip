@@ -740,7 +740,7 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     // ---- the full sweep of the point in LDS (TM_R, TM_T, TM_KC) into Gram block `dst`: main loop, cross-wave reduction, and
     // (with_stats) the statistics of the frame. Called a second time in a round whose residual-only sweep was not the solve's last.
     auto full_sweep = [&](const bool with_stats) {
-    d4 acc0, acc1;
+    GramBlocks acc;   // the ten upper 4 x 4 blocks of the wave's two chains (cc_gram_blocks.hpp)
     {
       CC_FRESH_TID(tid);
       const int ttid = tid & 255, lane = tid & 63;
@@ -753,8 +753,7 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
       for (int i = 0; i < 9; ++i) kk[i] = rfl(sm[TM_KC + i]);
       // ---- main loop: 64 observations per wave per pass, no barrier (k_intr_sweep's loop)
       double* stage = s_stage + wave * kStageDoublesPerWave;
-      acc0 = d4{0.0, 0.0, 0.0, 0.0};
-      acc1 = d4{0.0, 0.0, 0.0, 0.0};
+      gram_blocks_clear(acc);
       // (Waves that share a SIMD -- one per team -- enter the loop in lockstep. A start staggered by k sleep units per team, so that one
       // team's LDS staging falls under another's matrix products, was measured at several k and never paid: removed in round 6.)
       // (a wave without observations never reads its prefetch: said here, so that five registers are not held round the loop for it)
@@ -780,12 +779,12 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
         huber_row_u(kk, oc, ru, v, wrow);
         stage_row(stage, lane, v);
         wave_lds_fence();
-        gram_rows_ahead(stage, lane, acc0, acc1);
+        gram_blocks_ahead<kGbBatchPairs>(stage, lane, acc);
         wave_lds_fence();
         huber_row_v(kk, oc, rv, v, wrow);
         stage_row(stage, lane, v);
         wave_lds_fence();
-        gram_rows_ahead(stage, lane, acc0, acc1);
+        gram_blocks_ahead<kGbBatchPairs>(stage, lane, acc);
         wave_lds_fence();
       }
       // ---- cross-wave reduction of the 16 x 16 block into the frame's LDS slot
@@ -794,8 +793,7 @@ __global__ __launch_bounds__(TEAMS * 256, TEAMS) void k_intr_persist(IntrDev P, 
     {
       CC_FRESH_TID(tid);
       const int ttid = tid & 255, lane = tid & 63;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s_blk[twave * 256 + ((lane >> 4) + 4 * r) * 16 + (lane & 15)] = acc0[r] + acc1[r];
+      gram_blocks_store(acc, lane, s_blk + twave * 256);   // chain 0 + chain 1 of the wave, both triangles
       __syncthreads();
       const double g = gram_entry_held(mask, ttid) ? 0.0 : (s_blk[ttid] + s_blk[256 + ttid]) + (s_blk[512 + ttid] + s_blk[768 + ttid]);   // (constant coordinates: zero rows and columns)
       s_G[(team * 2 + dst) * 256 + ttid] = g;
