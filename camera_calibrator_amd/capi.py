@@ -122,6 +122,7 @@ EXPORTED_SYMBOLS = [
     "cc_distort_fisheye", "cc_undistort_fisheye",
     "cc_intrinsics_batch_set_model", "cc_intrinsics_batch_get_model", "cc_intrinsics_batch_estimate_model",
     "cc_intr_start_options_init", "cc_intrinsics_estimate_start_fisheye", "cc_intrinsics_start_scores", "cc_intrinsics_estimate_views_start",
+    "cc_intrinsics_batch_estimate_start_fisheye", "cc_intrinsics_batch_start_scores", "cc_intrinsics_batch_estimate_start",
 ]
 # EXTENSION: camera models of the single-camera solve (cc_solver.h)
 MODEL_RADTAN, MODEL_FISHEYE = 0, 1
@@ -202,6 +203,13 @@ def partition_frames(frame_offsets, nranks):
     _check(lib().cc_partition_frames(C.c_int64(len(off) - 1), _p(off, C.c_int64), C.c_int32(nranks),
                                      _p(first, C.c_int64)))
     return first
+
+
+def _start_report_dict(r):
+    """cc_intr_start_report as a dict (centre: a pair)."""
+    report = {k: getattr(r, k) for k, _ in IntrStartReport._fields_ if k != "centre"}
+    report["centre"] = (r.centre[0], r.centre[1])
+    return report
 
 
 def _summary_dict(s, log):
@@ -330,9 +338,7 @@ class IntrinsicsProblem:
         r = IntrStartReport()
         _check(lib().cc_intrinsics_estimate_start_fisheye(self._h, C.byref(o), _p(intr, C.c_double), _p(q, C.c_double),
                                                           _p(t, C.c_double), C.byref(r)))
-        report = {k: getattr(r, k) for k, _ in IntrStartReport._fields_ if k != "centre"}
-        report["centre"] = (r.centre[0], r.centre[1])
-        return intr, q, t, report
+        return intr, q, t, _start_report_dict(r)
 
     def start_scores(self):
         """(f [C], score [C], qualified [C]) of the last estimate_start_fisheye's search (cc_intrinsics_start_scores): the
@@ -628,6 +634,31 @@ class IntrinsicsBatch:
         _check(lib().cc_intrinsics_batch_solve(self._h, C.byref(options), ss))
         return [ss[p].iterations for p in range(self.n_problems)]
 
+    def estimate_start_fisheye(self, **options):
+        """EXTENSION: IntrinsicsProblem.estimate_start_fisheye for every problem of the batch at once
+        (cc_intrinsics_batch_estimate_start_fisheye; the handle's model must be MODEL_FISHEYE): seven launches whatever the
+        number of problems. `options`: the fields of cc_intr_start_options, one set for the whole batch. Returns
+        (intr [B, 9], q [Ftot, 4], t [Ftot, 3], [report_p]); the handle's state is not touched. A problem without a qualified
+        candidate raises; `last_start_reports` then holds every problem's report (best_candidate -1 marks such a problem)."""
+        o = intr_start_options(**options)
+        intr, q, t = np.zeros((self.n_problems, 9)), np.zeros((self.n_frames, 4)), np.zeros((self.n_frames, 3))
+        r = (IntrStartReport * self.n_problems)()
+        rc = lib().cc_intrinsics_batch_estimate_start_fisheye(self._h, C.byref(o), _p(intr, C.c_double), _p(q, C.c_double),
+                                                              _p(t, C.c_double), r)
+        self.last_start_reports = [_start_report_dict(r[p]) for p in range(self.n_problems)] if rc in (0, -5) else None
+        _check(rc)
+        return intr, q, t, self.last_start_reports
+
+    def start_scores(self):
+        """(f [B, C], score [B, C], qualified [B, C]) of the last estimate_start_fisheye's search
+        (cc_intrinsics_batch_start_scores), per problem as IntrinsicsProblem.start_scores returns them."""
+        n = 64 * self.n_problems
+        f, score, qualified = np.zeros(n), np.zeros(n), np.full(n, -1, dtype=np.int32)
+        _check(lib().cc_intrinsics_batch_start_scores(self._h, _p(f, C.c_double), _p(score, C.c_double), _p(qualified, C.c_int32)))
+        c = int((qualified >= 0).sum()) // self.n_problems   # (the library writes 0 or 1 for every candidate of the search, and only those)
+        shape = (self.n_problems, c)
+        return f[:c * self.n_problems].reshape(shape).copy(), score[:c * self.n_problems].reshape(shape).copy(), qualified[:c * self.n_problems].reshape(shape).copy()
+
 
 def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=None, device=0, log_capacity=1024, model=0):
     """One-shot cc_intrinsics_batch_optimize. problems: one (frame_offsets, uv, xyz) per problem; intr [B][9]; q, t: one array
@@ -660,12 +691,22 @@ def intrinsics_batch_optimize(problems, intr, q, t, const_mask=None, options=Non
 
 
 def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, options=None, device=0, log_capacity=1024, huber_a=None,
-                              model=0):
+                              model=0, start="zhang", start_options=None):
     """cc_intrinsics_batch_estimate (Zhang initialisation per problem + the batched solve). distortion5: [B][5] or None;
     const_mask: one per problem or None; huber_a: one Huber threshold in pixels per problem (the extension
     cc_intrinsics_batch_estimate_huber) or None; model != 0: the extension cc_intrinsics_batch_estimate_model, one model for
     the whole batch, huber_a passed on, `distortion5` then [B][4] (k1..k4) or [B][5] with the fifth entry ignored.
+    start="fisheye": the extension cc_intrinsics_batch_estimate_start, the batched focal-length search of
+    IntrinsicsBatch.estimate_start_fisheye in place of the per-problem Zhang launches (model must be MODEL_FISHEYE;
+    start_options: a dict of cc_intr_start_options fields or an IntrStartOptions, one for the whole batch); start="zhang" (or
+    None), the default, is the call as it was.
     Returns (K_init float32 [B][3][3], intr [B][9], [q_p], [t_p], [summary_p])."""
+    if start is None:
+        start = "zhang"
+    if start not in ("zhang", "fisheye"):
+        raise ValueError(f"start must be 'zhang' or 'fisheye', not {start!r}")
+    if start == "zhang" and start_options is not None:
+        raise ValueError("start_options belong to start='fisheye'")
     poff, foff, uv, xyz = _batch_layout(problems)
     B, F = len(poff) - 1, int(poff[-1])
     K = np.zeros((B, 9), dtype=np.float32)
@@ -677,7 +718,18 @@ def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, optio
     mask = np.zeros(B, dtype=np.uint32) if const_mask is None else np.ascontiguousarray(const_mask, dtype=np.uint32)
     opt = options if options is not None else default_options()
     ss, logs = _batch_summaries(B, log_capacity)
-    if model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
+    if start == "fisheye":
+        so = start_options if isinstance(start_options, IntrStartOptions) else intr_start_options(**(start_options or {}))
+        ha = None
+        if huber_a is not None:
+            ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
+            assert ha.size == B
+        _check(lib().cc_intrinsics_batch_estimate_start(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                                        _p(t, C.c_double), ss, _p(ha, C.c_double) if ha is not None else None,
+                                                        C.c_int32(model), C.byref(so)))
+    elif model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
         ha = None
         if huber_a is not None:
             ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))

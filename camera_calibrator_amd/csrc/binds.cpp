@@ -171,7 +171,13 @@ PYBIND11_MODULE(pycalibrator, m) {
       .def("LastFinalCost", &Calibrator::LastFinalCost);
 
   // extension: several cameras' Estimate() in one call, their bundle adjustments batched on the GPU
-  m.def("EstimateMany", &Calibrator::EstimateMany, py::arg("calibrators"), py::arg("img_points"), py::arg("world_points"));
+  using ManyPoints2D = std::vector<std::vector<calibrator::Points2D>>;
+  using ManyPoints3D = std::vector<std::vector<calibrator::Points3D>>;
+  m.def("EstimateMany", static_cast<void (*)(const std::vector<Calibrator*>&, const ManyPoints2D&, const ManyPoints3D&)>(&Calibrator::EstimateMany),
+        py::arg("calibrators"), py::arg("img_points"), py::arg("world_points"));
+  // extension: the start of the whole batch as a fourth, required argument (Start.FisheyeFocalSearch: every calibrator Fisheye)
+  m.def("EstimateMany", static_cast<void (*)(const std::vector<Calibrator*>&, const ManyPoints2D&, const ManyPoints3D&, calibrator::Start)>(&Calibrator::EstimateMany),
+        py::arg("calibrators"), py::arg("img_points"), py::arg("world_points"), py::arg("start"));
 
   py::class_<ExtrinsicsCalibrator>(m, "ExtrinsicsCalibrator")
       .def(py::init<>())

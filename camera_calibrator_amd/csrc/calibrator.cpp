@@ -191,6 +191,21 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
 // the batch's one sweep kernel carries one model; a rig with both kinds of lens calls EstimateMany once per kind.
 void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
                               const std::vector<std::vector<Points3D>>& world_points) {
+  EstimateManyFrom(calibrators, img_points, world_points, nullptr);
+}
+
+// EXTENSION: the start belongs to the batch, like the model: `start` decides, the calibrators' own SetStart is not consulted.
+// Zhang: the call above. FisheyeFocalSearch: cc_intrinsics_batch_estimate_start at the library's default options -- the search of
+// every camera in one stream of launches in place of the per-camera Zhang launches; every calibrator must have the fisheye model.
+void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                              const std::vector<std::vector<Points3D>>& world_points, Start start) {
+  if (start != Start::Zhang && start != Start::FisheyeFocalSearch) throw std::invalid_argument("Calibrator::EstimateMany: unknown start");
+  EstimateManyFrom(calibrators, img_points, world_points, &start);
+}
+
+// batch_start NULL: the three-argument form, which refuses calibrators with a start of their own set
+void Calibrator::EstimateManyFrom(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                                  const std::vector<std::vector<Points3D>>& world_points, const Start* batch_start) {
   const size_t B = calibrators.size();
   if (img_points.size() != B || world_points.size() != B)
     throw std::invalid_argument("Calibrator::EstimateMany: calibrators, img_points and world_points must have the same length");
@@ -212,8 +227,14 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   }
   const size_t F = foff.size() - 1;
   const CameraModel model = calibrators[0]->model_;
+  const bool focal_search = batch_start && *batch_start == Start::FisheyeFocalSearch;
+  if (focal_search)   // (refused before anything is packed)
+    for (size_t p = 0; p < B; ++p)
+      if (calibrators[p]->model_ != CameraModel::Fisheye)
+        throw std::invalid_argument("Calibrator::EstimateMany: the focal-length search is a start of the fisheye model; every calibrator "
+                                    "needs SetCameraModel(Fisheye)");
   for (size_t p = 0; p < B; ++p)
-    if (calibrators[p]->start_ != Start::Zhang)
+    if (!batch_start && calibrators[p]->start_ != Start::Zhang)
       throw std::invalid_argument("Calibrator::EstimateMany: a calibrator has the focal-length search set (SetStart); the batch starts from "
                                   "Zhang's initialisation -- call Estimate on that calibrator");
   for (size_t p = 1; p < B; ++p)   // (refused before anything is packed)
@@ -248,7 +269,13 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
   cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
   std::vector<cc_summary> summaries(B);
   std::memset(summaries.data(), 0, B * sizeof(cc_summary));
-  const int rc = fisheye
+  cc_intr_start_options start_options;
+  cc_intr_start_options_init(&start_options);
+  const int rc = focal_search
+      ? cc_intrinsics_batch_estimate_start(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
+                                           any_huber ? huber.data() : nullptr, CC_MODEL_FISHEYE, &start_options)
+      : fisheye
       ? cc_intrinsics_batch_estimate_model(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
                                            dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
                                            any_huber ? huber.data() : nullptr, CC_MODEL_FISHEYE)
@@ -270,6 +297,7 @@ void Calibrator::EstimateMany(const std::vector<Calibrator*>& calibrators, const
     c.last_solver_note_.clear();
     for (double& v : c.last_timing_ms_) v = 0.0;
     c.last_timing_ms_[6] = ms;
+    if (focal_search) c.last_start_focal_ = K9[9 * p];   // (float32, as Estimate sets it)
     for (int r = 0; r < 3; ++r) for (int col = 0; col < 3; ++col) c.camera_matrix_(r, col) = K9[9 * p + r * 3 + col];
     c.camera_matrix_(0, 0) = static_cast<float>(k[FX]);
     c.camera_matrix_(1, 1) = static_cast<float>(k[FY]);

@@ -55,6 +55,14 @@ class Calibrator {
   /// conditions Estimate() throws for.
   static void EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
                            const std::vector<std::vector<Points3D>>& world_points);
+  /// EXTENSION: EstimateMany with the start chosen for the whole batch. The start belongs to the batch, like the model: `start`
+  /// decides and the calibrators' own SetStart is not consulted. Start::Zhang is the call above. Start::FisheyeFocalSearch runs
+  /// the focal-length search of SetStart for every camera in one stream of launches (cc_intrinsics_batch_estimate_start at the
+  /// library's default options) in place of the per-camera Zhang launches: every calibrator must have the Fisheye model, else
+  /// std::invalid_argument before anything is packed; each calibrator's LastStartFocal() becomes its own camera's focal length. A
+  /// view the search cannot place, or a camera without a winner, throws std::runtime_error naming camera and view.
+  static void EstimateMany(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                           const std::vector<std::vector<Points3D>>& world_points, Start start);
 
   // ---- mapping points through the model ------------------------------------------------------------
   /// pixels -> undistorted normalised coordinates (reference: calibrator.cpp:118-155)
@@ -90,8 +98,8 @@ class Calibrator {
   /// equidistant lens on bearing vectors with every view's pose at the picked one (cc_intrinsics_estimate_views_start at the
   /// library's default options), for boards that stand round the lens and beyond 90 degrees off its axis, where Zhang's start
   /// costs several times the iterations or ends in a wrong basin. With the radial-tangential model Estimate throws
-  /// std::invalid_argument, and so it does when SetDevices selected several devices; EstimateMany throws when any of its
-  /// calibrators has the search set (the batch keeps Zhang). A view the search cannot place throws std::runtime_error naming it.
+  /// std::invalid_argument, and so it does when SetDevices selected several devices; the three-argument EstimateMany throws when any
+  /// of its calibrators has the search set (the batch's start is an argument of the four-argument form). A view the search cannot place throws std::runtime_error naming it.
   void SetStart(Start start);
   Start GetStart() const { return start_; }
   /// The focal length the last Estimate's search picked, in float32 as K holds it (the start's K is handed over as float32, like
@@ -120,6 +128,9 @@ class Calibrator {
 
  private:
   void ReadSolverStatus();
+  // the body of both EstimateMany forms; batch_start NULL: the three-argument form
+  static void EstimateManyFrom(const std::vector<Calibrator*>& calibrators, const std::vector<std::vector<Points2D>>& img_points,
+                               const std::vector<std::vector<Points3D>>& world_points, const Start* batch_start);
   int image_w_;
   int image_h_;
   int device_{0};

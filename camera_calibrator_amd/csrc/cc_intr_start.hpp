@@ -41,6 +41,21 @@ struct IntrStartDev {
   int32_t* kind;            // [F]
 };
 
+// Host checks both the single and the batched start make (cc_intr_start_host.hpp, cc_intr_start_batch_host.hpp), no device call.
+inline int64_t intr_start_searched(const cc_intr_start_options& o, int64_t F) {
+  return o.search_views <= 0 || o.search_views >= F ? F : (int64_t)o.search_views;
+}
+
+inline int intr_start_check(const cc_intr_start_options& o, const char* who) {
+  if (o.candidates < 1 || o.candidates > kIntrStartMaxCandidates)
+    return fail(CC_ERR_BAD_ARGUMENT, "%s: candidates must be in 1 .. %d", who, kIntrStartMaxCandidates);
+  if (!(o.theta_lo > 0.0) || !(o.theta_hi < 3.14159265358979323846) || !(o.theta_hi >= o.theta_lo))
+    return fail(CC_ERR_BAD_ARGUMENT, "%s: needs 0 < theta_lo <= theta_hi < pi", who);
+  if (o.search_views < 0) return fail(CC_ERR_BAD_ARGUMENT, "%s: search_views must be >= 0 (0: every view)", who);
+  if (o.refine_iterations < 0 || o.refine_iterations > 1000) return fail(CC_ERR_BAD_ARGUMENT, "%s: refine_iterations must be in 0 .. 1000", who);
+  return CC_OK;
+}
+
 // Everything of one start on the stream, not waited for: extent, candidates, search, pick, pose pass. `marks` (may be NULL):
 // four events recorded before the extent, after it, after the pick and after the pose pass.
 void intr_start_enqueue(const IntrStartDev& P, hipStream_t s, int refine_iterations, hipEvent_t* marks);

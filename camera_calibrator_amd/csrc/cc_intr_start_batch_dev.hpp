@@ -1,28 +1,24 @@
-// cc_intr_start_dev.hpp -- the kernels of the fisheye focal-length start (cc_intr_start.hpp), in a header so that cc_intr_start.hip
-// is the launch only. k_intr_start_view is k_rig_start_view_bearing (cc_rig_start_bearing_dev.hpp) with the bearing of
-// observation i formed in fp64 from its pixel, the centre and the candidate focal length instead of read from a float3 buffer,
-// written a second time on the helpers both share (cc_rig_start_math.hpp, cc_device.hpp, cc_eigen_dev.hpp): with the body as a
-// function that both kernels instantiate, k_rig_start_view_bearing does not keep its text. One step differs: the
-// null vector's inverse iteration goes on past its twelve steps until it has settled (smallest_eigvec_settled says why).
-// The helpers of these kernels are in cc_intr_start_math.hpp and the lines of one (view, candidate) wave in
-// cc_intr_start_view_body.hpp: the batch's kernels (cc_intr_start_batch_dev.hpp) are built from both.
+// cc_intr_start_batch_dev.hpp -- the kernels of the batched fisheye focal-length start (cc_intr_start_batch.hpp), in a header so
+// that cc_intr_start_batch.hip is the launch only. Each is its single-problem kernel (cc_intr_start_dev.hpp) with the problem's
+// IntrStartDev read from the device table instead of passed by value, on the same helpers (cc_intr_start_math.hpp); the view
+// kernel's wave is compiled from the same lines (cc_intr_start_view_body.hpp).
 #pragma once
 
-#include "cc_intr_start.hpp"
+#include "cc_intr_start_batch.hpp"
 #include "cc_intr_start_math.hpp"
 
 namespace cc {
 
-// pass 0: the bounding box of the finite pixels; pass 1: r_max, their largest distance from the centre (any grid: max and min do
-// not depend on the order); pass 2, one wave: the centre, r_max and the candidates f_j = r_max / theta_j as doubles.
-// A pixel is finite when both its coordinates are. No product is fused into a sum here: the values are the ones IEEE arithmetic
-// gives on any machine.
-__global__ __launch_bounds__(256) void k_intr_start_extent(IntrStartDev P, int pass) {
+// pass 0 / pass 1, grid T.E, 256 threads: workgroup w owns observations [begin, end) of one problem, a pixel a thread and pass of
+// the loop; one atomic per word and workgroup on that problem's words. pass 2, grid T.B, one wave: problem blockIdx.x's centre,
+// r_max and candidates. The expressions are k_intr_start_extent's, none fused: maxima and minima do not depend on the grid.
+__global__ __launch_bounds__(256) void k_intrb_start_extent(IntrStartBatchDev T, int pass) {
 #pragma clang fp contract(off)
   __shared__ unsigned long long s_max[4][4];   // the waves' maxima of a workgroup
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = (blockDim.x + 63) >> 6;
   if (pass == 2) {
-    if (blockIdx.x || threadIdx.x >= 64) return;
+    if ((int64_t)blockIdx.x >= T.B || threadIdx.x >= 64) return;
+    const IntrStartDev P = T.prob[blockIdx.x];
     double cx, cy;
     intr_start_centre(P, cx, cy);
     const double r_max = __longlong_as_double((long long)P.box[4]);
@@ -33,11 +29,13 @@ __global__ __launch_bounds__(256) void k_intr_start_extent(IntrStartDev P, int p
     }
     return;
   }
+  if ((int64_t)blockIdx.x >= T.E) return;
+  const IntrStartExtentWg wg = T.extent[blockIdx.x];
+  const IntrStartDev P = T.prob[wg.problem];
   const float2* __restrict__ uv2 = reinterpret_cast<const float2*>(P.uv);
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   if (pass == 0) {
     unsigned long long lo_u = 0, hi_u = 0, lo_v = 0, hi_v = 0;   // (0: below the word of every finite float)
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.N; i += stride) {
+    for (int64_t i = wg.begin + threadIdx.x; i < wg.end; i += blockDim.x) {
       const float2 p = uv2[i];
       if (!(isfinite(p.x) && isfinite(p.y))) continue;
       const unsigned long long wu = start_order_word(p.x), wv = start_order_word(p.y);
@@ -48,7 +46,7 @@ __global__ __launch_bounds__(256) void k_intr_start_extent(IntrStartDev P, int p
     lo_u = wave_max_u64(lo_u); hi_u = wave_max_u64(hi_u); lo_v = wave_max_u64(lo_v); hi_v = wave_max_u64(hi_v);
     if (lane == 0) { s_max[wave][0] = lo_u; s_max[wave][1] = hi_u; s_max[wave][2] = lo_v; s_max[wave][3] = hi_v; }
     __syncthreads();
-    if (threadIdx.x < 4) {   // one atomic per word and workgroup: they all land on the same four addresses
+    if (threadIdx.x < 4) {
       unsigned long long m = s_max[0][threadIdx.x];
       for (int w = 1; w < nwaves; ++w) m = s_max[w][threadIdx.x] > m ? s_max[w][threadIdx.x] : m;
       if (m) atomicMax(P.box + threadIdx.x, m);
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(256) void k_intr_start_extent(IntrStartDev P, int p
   double cx, cy;
   intr_start_centre(P, cx, cy);
   unsigned long long r = 0;   // (a non-negative double's bits order as the double does)
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.N; i += stride) {
+  for (int64_t i = wg.begin + threadIdx.x; i < wg.end; i += blockDim.x) {
     const float2 p = uv2[i];
     if (!(isfinite(p.x) && isfinite(p.y))) continue;
     const double d0 = (double)p.x - cx, d1 = (double)p.y - cy;
@@ -76,15 +74,18 @@ __global__ __launch_bounds__(256) void k_intr_start_extent(IntrStartDev P, int p
   }
 }
 
-// ---- one (view, candidate) pair -------------------------------------------------------------------------------------------------
-// Grid (views, candidates), one wave each. pose_pass 0, the search: block (k, j) is searched view floor(k F / S) through candidate
-// j, its record goes to P.srec / P.skind [j][k]. pose_pass 1: block (v, 0) is view v through the picked candidate, its record goes
-// to P.view / P.kind [v]; nothing is written when no candidate qualified. A searched view comes out of the two passes with the
-// same bits: the same instructions on the same inputs. What the wave does: cc_intr_start_view_body.hpp.
-__global__ __launch_bounds__(64) void k_intr_start_view(IntrStartDev P, int pose_pass, int refine_iterations) {
+// Grid (workgroups, candidates), one wave each. pose_pass 0, the search: workgroup x is T.search_where[x] = {problem, k}, searched
+// view floor(k F / S) of that problem through candidate blockIdx.y, its record goes to the problem's srec / skind [j][k].
+// pose_pass 1: workgroup x is T.view_where[x] = {problem, view} through that problem's picked candidate, its record goes to the
+// problem's view / kind; nothing is written for a problem without a qualified candidate. From there on the wave runs
+// k_intr_start_view's lines on the problem's IntrStartDev.
+__global__ __launch_bounds__(64) void k_intrb_start_view(IntrStartBatchDev T, int pose_pass, int refine_iterations) {
   __shared__ __attribute__((aligned(16))) double s_stage[kStageDoublesPerWave];
   const int lane = threadIdx.x;
-  int64_t v = blockIdx.x;
+  if ((int64_t)blockIdx.x >= (pose_pass ? T.Ftot : T.Stot)) return;
+  const int2 wh = pose_pass ? T.view_where[blockIdx.x] : T.search_where[blockIdx.x];
+  const IntrStartDev P = T.prob[wh.x];
+  int64_t v = wh.y;
   int j = blockIdx.y;
   double* out;
   int32_t* kind_out;
@@ -102,11 +103,11 @@ __global__ __launch_bounds__(64) void k_intr_start_view(IntrStartDev P, int pose
 #include "cc_intr_start_view_body.hpp"
 }
 
-// ---- pick -----------------------------------------------------------------------------------------------------------------------
-// One wave, lane j = candidate j: S_j = f_j^2 sum_k cost_{j,k} over the searched views k in index order (a serial sum per lane:
-// the same bits on every call). A candidate with a searched view whose record is invalid is disqualified, unless that view is
-// invalid for every candidate; the smallest S_j among the qualified wins, the lowest index on ties.
-__global__ __launch_bounds__(64) void k_intr_start_pick(IntrStartDev P) {
+// Grid T.B, one wave per problem, lane j = candidate j: k_intr_start_pick on the problem's IntrStartDev -- S_j = f_j^2 sum_k
+// cost_{j,k} over the problem's searched views k in index order, a serial sum per lane.
+__global__ __launch_bounds__(64) void k_intrb_start_pick(IntrStartBatchDev T) {
+  if ((int64_t)blockIdx.x >= T.B) return;
+  const IntrStartDev P = T.prob[blockIdx.x];
   const int j = threadIdx.x;
   const bool live = j < P.C;
   double sum = 0.0;

@@ -22,19 +22,7 @@ struct IntrStartLayout {
   }
 };
 
-static int64_t intr_start_searched(const cc_intr_start_options& o, int64_t F) {
-  return o.search_views <= 0 || o.search_views >= F ? F : (int64_t)o.search_views;
-}
-
-static int intr_start_check(const cc_intr_start_options& o, const char* who) {
-  if (o.candidates < 1 || o.candidates > kIntrStartMaxCandidates)
-    return fail(CC_ERR_BAD_ARGUMENT, "%s: candidates must be in 1 .. %d", who, kIntrStartMaxCandidates);
-  if (!(o.theta_lo > 0.0) || !(o.theta_hi < 3.14159265358979323846) || !(o.theta_hi >= o.theta_lo))
-    return fail(CC_ERR_BAD_ARGUMENT, "%s: needs 0 < theta_lo <= theta_hi < pi", who);
-  if (o.search_views < 0) return fail(CC_ERR_BAD_ARGUMENT, "%s: search_views must be >= 0 (0: every view)", who);
-  if (o.refine_iterations < 0 || o.refine_iterations > 1000) return fail(CC_ERR_BAD_ARGUMENT, "%s: refine_iterations must be in 0 .. 1000", who);
-  return CC_OK;
-}
+// (intr_start_searched, intr_start_check: cc_intr_start.hpp -- the batch's host side, cc_intr_start_batch_host.hpp, takes them too)
 
 // The start on the handle's device observations, in `work` (IntrStartLayout(F, candidates, searched views) bytes). Writes nothing
 // to the handle's state. first_invalid (may be NULL): the first view without a pose, -1: none. `timed` (scripts: cc_intrinsics_debug_start_marks): hipEvents

@@ -20,6 +20,7 @@
 #include "cc_device.hpp"
 #include "cc_intrinsics_dev.hpp"
 #include "cc_intrinsics_batch_dev.hpp"
+#include "cc_intr_start_batch.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -600,6 +601,14 @@ struct cc_intrinsics_batch {
   bool huber_on = false;           // ... on for at least one problem: the solve launches k_intrb_sweep_huber behind k_intrb_sweep
   bool huber_all = false;          // ... on for every problem: k_intrb_sweep has nothing to sweep and is left out
   int model = CC_MODEL_RADTAN;     // EXTENSION (cc_intrinsics_batch_set_model): CC_MODEL_FISHEYE -> k_intrb_sweep_fisheye sweeps every problem
+  // EXTENSION (cc_intrinsics_batch_estimate_start_fisheye, cc_intr_start_batch_host.hpp): the start's device scratch, grown on demand,
+  // and where the last search's tables lie in it ([B][kIntrStartMaxCandidates] each; start_candidates 0: no search yet)
+  std::vector<int64_t> foff;       // [Ftot + 1] the frame offsets as uploaded (the start's workgroup tables are built from them)
+  void* start_work = nullptr;
+  size_t start_work_bytes = 0;
+  int start_candidates = 0;
+  const double *start_f = nullptr, *start_score = nullptr;
+  const int32_t* start_qualified = nullptr;
 };
 
 namespace cc {
@@ -611,6 +620,7 @@ static void batch_destroy(cc_intrinsics_batch* h) {
   if (h->stream) { stream_ok = hipStreamSynchronize(h->stream) == hipSuccess; (void)hipGetLastError(); }
   if (h->arena) arena_put(h->device, h->arena, h->arena_cached);
   if (h->h_ctl) hipHostFree(h->h_ctl);
+  if (h->start_work) (void)hipFree(h->start_work);
   if (stream_ok) stream_put(h->device, h->stream);
   else if (h->stream) hipStreamDestroy(h->stream);
   delete h;
@@ -699,6 +709,7 @@ static int batch_create(const char* who, int32_t device, int64_t B, const int64_
   h->device = device; h->B = B; h->Ftot = Ftot; h->N = N;
   h->first.swap(first);
   h->where.swap(where);
+  h->foff.assign(frame_offsets, frame_offsets + Ftot + 1);
   const size_t extra = extra_per_frame * (size_t)Ftot + extra_per_problem * (size_t)B;
   if (int rc = batch_create_impl(h, frame_offsets, uv, xyz, extra, wait)) { batch_destroy(h); return rc; }
   *out = h;
@@ -977,3 +988,7 @@ int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t 
 }
 
 }  // extern "C"
+
+// EXTENSION: the fisheye focal-length start for every problem of a batch (cc_intrinsics_batch_estimate_start_fisheye,
+// cc_intrinsics_batch_start_scores, cc_intrinsics_batch_estimate_start)
+#include "cc_intr_start_batch_host.hpp"

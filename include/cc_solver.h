@@ -344,7 +344,8 @@ int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, in
  *      focal lengths). A candidate with a searched view it cannot place is disqualified, unless no candidate places that view.
  *      The smallest S_j among the qualified candidates wins, the lowest index on ties.
  *   6. every view's pose at the winner (the searched views come out again with the same bits).
- * Out of scope: the batch (cc_intrinsics_batch_* keeps Zhang), the radial-tangential model, estimating k or a non-square pixel
+ * The batch has the same start for all its problems at once (cc_intrinsics_batch_estimate_start_fisheye, below).
+ * Out of scope: the radial-tangential model, estimating k or a non-square pixel
  * in the start, interpolation between candidates, multi-GPU handles, the persistent kernel; no entry point takes this start by
  * default, and the rig solve does not take its result by itself (cc_rigk_set_intrinsics is the caller's second call).
  * ------------------------------------------------------------------------------------------- */
@@ -450,6 +451,34 @@ int cc_intrinsics_batch_estimate_model(const cc_options* opt, int32_t device, in
                                        const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
                                        const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
                                        cc_summary* summaries, const double* huber_a, int32_t model);
+/* EXTENSION: the fisheye focal-length start (cc_intrinsics_estimate_start_fisheye, above) for EVERY problem of a batch handle
+ * whose model is CC_MODEL_FISHEYE (any other handle: CC_ERR_STATE), as one stream of seven launches whatever the number of
+ * problems -- the boxes' zeroing, bounding boxes, r_max, centres and candidates, the search over (searched view of any
+ * problem) x candidate, the pick, the pose pass over all views -- and one host wait. ONE cc_intr_start_options
+ * for the whole batch (NULL: the defaults; out of range: CC_ERR_BAD_ARGUMENT before any device call); a finite `centre` applies
+ * to every problem; search_views selects per problem: every view of a problem with no more views than that, else its views
+ * floor(k F_p / S). Per problem the outputs are what the single call defines, and they do not depend on what else is in the
+ * batch or where the problem sits in it: intr9 [B][9] = (f, f, c_x, c_y, 0, ...), q_wxyz [Ftot][4] / t_xyz [Ftot][3] with
+ * q = (1, 0, 0, 0), t = 0 for a view that is invalid by its own data, counted in reports[p].views_invalid; reports [B]. Every
+ * output may be NULL. The handle's state is not touched. A problem without a qualified candidate: CC_ERR_STATE, all B reports
+ * are filled (best_candidate = -1 and views_invalid = 0 mark such a problem), the message names the first one, and nothing else
+ * is written. */
+int cc_intrinsics_batch_estimate_start_fisheye(cc_intrinsics_batch* h, const cc_intr_start_options* opt, double* intr9,
+                                               double* q_wxyz, double* t_xyz, cc_intr_start_report* reports);
+/* The last search of the handle: f, score (S_j), qualified, [B][C] each with C the candidates of that search (each may be
+ * NULL). CC_ERR_STATE before any start. */
+int cc_intrinsics_batch_start_scores(cc_intrinsics_batch* h, double* f, double* score, int32_t* qualified);
+/* cc_intrinsics_batch_estimate_model with the start chosen. start NULL: that call, bit for bit (Zhang). Otherwise the model
+ * must be CC_MODEL_FISHEYE (CC_ERR_BAD_ARGUMENT), the batched search replaces the per-problem Zhang launches, K_init9[p]
+ * receives (f, 0, c_x; 0, f, c_y; 0, 0, 1) and the distortion starts from distortion5[p]'s four values (NULL: zeros). Every
+ * problem needs >= 3 frames. A view without a pose at its problem's winner, or a problem without a winner:
+ * CC_ERR_BAD_ARGUMENT, the message names the problem (and the view, by its index within the problem). The argument checks come
+ * before the device is selected. */
+int cc_intrinsics_batch_estimate_start(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q_wxyz, double* t_xyz,
+                                       cc_summary* summaries, const double* huber_a, int32_t model,
+                                       const cc_intr_start_options* start);
 
 /* Contiguous frame partition balanced by observation count (host logic, no GPU needed).
  * first_frame has nranks+1 entries; rank r owns frames [first_frame[r], first_frame[r+1]). */

@@ -22,7 +22,7 @@ import subprocess
 import sys
 import tempfile
 
-UNITS = ["cc_rig.hip", "cc_rig_inner.hip", "cc_rig_lens.hip", "cc_rig_start.hip", "cc_rig_start_bearing.hip", "cc_rigk_start.hip", "cc_zhang.hip", "cc_intrinsics.hip", "cc_intr_start.hip", "cc_intrinsics_batch_fisheye.hip", "cc_intrinsics_batch.hip", "cc_intrinsics_batch_huber.hip",
+UNITS = ["cc_rig.hip", "cc_rig_inner.hip", "cc_rig_lens.hip", "cc_rig_start.hip", "cc_rig_start_bearing.hip", "cc_rigk_start.hip", "cc_zhang.hip", "cc_intrinsics.hip", "cc_intr_start.hip", "cc_intr_start_batch.hip", "cc_intrinsics_batch_fisheye.hip", "cc_intrinsics_batch.hip", "cc_intrinsics_batch_huber.hip",
          "cc_intrinsics_persist.hip", "cc_points.hip"]
 FLAGS = {"cc_points.hip": ["-ffp-contract=off"]}
 
