@@ -212,6 +212,14 @@ def _start_report_dict(r):
     return report
 
 
+def _summary(log_capacity):
+    """(Summary with a log of log_capacity rows, the log): what a solve call fills and _summary_dict reads."""
+    log = (Iteration * max(1, log_capacity))()
+    s = Summary()
+    s.log, s.log_capacity = C.cast(log, C.POINTER(Iteration)), log_capacity
+    return s, log
+
+
 def _summary_dict(s, log):
     names = [f[0] for f in Iteration._fields_]
     return {
@@ -278,10 +286,7 @@ class IntrinsicsProblem:
 
     def solve(self, options=None, log_capacity=1024):
         opt = options if options is not None else default_options()
-        log = (Iteration * max(1, log_capacity))()
-        s = Summary()
-        s.log = C.cast(log, C.POINTER(Iteration))
-        s.log_capacity = log_capacity
+        s, log = _summary(log_capacity)
         _check(lib().cc_intrinsics_solve(self._h, C.byref(opt), C.byref(s)))
         return _summary_dict(s, log)
 
@@ -420,44 +425,28 @@ def intrinsics_optimize(frame_offsets, uv, xyz, intr, q, t, const_mask=0, option
     uv, xyz = _f32(uv), _f32(xyz)
     intr, q, t = _f64(intr).copy(), _f64(q).copy(), _f64(t).copy()
     opt = options if options is not None else default_options()
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
-    if model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
-        if devices is not None:
-            raise ValueError("model is for one device only")
-        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_optimize_views_model(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                        _p(counts, C.c_int64), _p(intr, C.c_double), C.c_uint32(const_mask),
-                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
-                                                        C.c_int32(model)))
-        return intr, q, t, _summary_dict(s, log)
-    if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
-        if devices is not None:
-            raise ValueError("huber_a is for one device only")
-        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_optimize_views_huber(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                        _p(counts, C.c_int64), _p(intr, C.c_double), C.c_uint32(const_mask),
-                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a)))
-        return intr, q, t, _summary_dict(s, log)
-    if devices is not None:
+    s, log = _summary(log_capacity)
+    # The symbol and what it takes behind the shared arguments. model 0 and huber_a <= 0 are off: the symbols without them; an
+    # unknown model or a NaN threshold goes on to the C side, which refuses it.
+    where, loss = (C.c_int32(device),), not huber_a <= 0
+    if (model != 0 or loss) and devices is not None:
+        raise ValueError(("model" if model != 0 else "huber_a") + " is for one device only")
+    if model != 0:
+        name, tail = "cc_intrinsics_optimize_views_model", (C.c_double(huber_a), C.c_int32(model))
+    elif loss:
+        name, tail = "cc_intrinsics_optimize_views_huber", (C.c_double(huber_a),)
+    elif devices is not None:
         devs = np.ascontiguousarray(devices, dtype=np.int32)
-        _check(lib().cc_intrinsics_optimize_multi(C.byref(opt), C.c_int32(len(devs)), _p(devs, C.c_int32), C.c_int64(F),
-                                                  _p(off, C.c_int64), _p(uv, C.c_float), _p(xyz, C.c_float),
-                                                  _p(intr, C.c_double), C.c_uint32(const_mask),
-                                                  _p(q, C.c_double), _p(t, C.c_double), C.byref(s)))
-        return intr, q, t, _summary_dict(s, log)
-    if views:
+        name, tail, where = "cc_intrinsics_optimize_multi", (), (C.c_int32(len(devs)), _p(devs, C.c_int32))
+    else:
+        name, tail = "cc_intrinsics_optimize_views" if views else "cc_intrinsics_optimize", ()
+    if "_views" in name:
         uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_optimize_views(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                  _p(counts, C.c_int64), _p(intr, C.c_double), C.c_uint32(const_mask),
-                                                  _p(q, C.c_double), _p(t, C.c_double), C.byref(s)))
-        return intr, q, t, _summary_dict(s, log)
-    _check(lib().cc_intrinsics_optimize(C.byref(opt), C.c_int32(device), C.c_int64(F),
-                                        _p(off, C.c_int64), _p(uv, C.c_float), _p(xyz, C.c_float),
-                                        _p(intr, C.c_double), C.c_uint32(const_mask),
-                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s)))
+        obs = (uv_views, xyz_views, _p(counts, C.c_int64))
+    else:
+        obs = (_p(off, C.c_int64), _p(uv, C.c_float), _p(xyz, C.c_float))
+    _check(getattr(lib(), name)(C.byref(opt), *where, C.c_int64(F), *obs, _p(intr, C.c_double), C.c_uint32(const_mask),
+                                _p(q, C.c_double), _p(t, C.c_double), C.byref(s), *tail))
     return intr, q, t, _summary_dict(s, log)
 
 
@@ -479,48 +468,29 @@ def intrinsics_estimate(frame_offsets, uv, xyz, distortion5=None, const_mask=0, 
     F = len(off) - 1
     uv, xyz = _f32(uv), _f32(xyz)
     opt = options if options is not None else default_options()
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
+    s, log = _summary(log_capacity)
     K = np.zeros(9, dtype=np.float32)
     intr, q, t = np.zeros(9), np.zeros((F, 4)), np.zeros((F, 3))
     d5 = _f64(distortion5) if distortion5 is not None else None
+    # The symbol and what it takes behind the shared arguments. model 0 and huber_a <= 0 are off: the symbols without them; a
+    # NaN threshold goes on to the C side, which refuses it.
     if start == "fisheye":
         so = start_options if isinstance(start_options, IntrStartOptions) else intr_start_options(**(start_options or {}))
+        name, tail = "cc_intrinsics_estimate_views_start", (C.c_double(huber_a), C.c_int32(model), C.byref(so))
+    elif model != 0:
+        name, tail = "cc_intrinsics_estimate_views_model", (C.c_double(huber_a), C.c_int32(model))
+    elif not huber_a <= 0:
+        name, tail = "cc_intrinsics_estimate_views_huber", (C.c_double(huber_a),)
+    else:
+        name, tail = "cc_intrinsics_estimate_views" if views else "cc_intrinsics_estimate", ()
+    if "_views" in name:
         uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_estimate_views_start(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
-                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
-                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
-                                                        C.c_int32(model), C.byref(so)))
-        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
-    if model != 0:   # (0 is off: the symbols without a model argument, below)
-        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_estimate_views_model(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
-                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
-                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a),
-                                                        C.c_int32(model)))
-        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
-    if not huber_a <= 0:   # (<= 0 is off: the symbols without the loss, below; NaN goes on to the C side, which refuses it)
-        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_estimate_views_huber(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                        _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
-                                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
-                                                        _p(q, C.c_double), _p(t, C.c_double), C.byref(s), C.c_double(huber_a)))
-        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
-    if views:
-        uv_views, xyz_views, counts, _keep = _views(off, uv, xyz)
-        _check(lib().cc_intrinsics_estimate_views(C.byref(opt), C.c_int32(device), C.c_int64(F), uv_views, xyz_views,
-                                                  _p(counts, C.c_int64), _p(d5, C.c_double) if d5 is not None else None,
-                                                  C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double),
-                                                  _p(q, C.c_double), _p(t, C.c_double), C.byref(s)))
-        return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
-    _check(lib().cc_intrinsics_estimate(C.byref(opt), C.c_int32(device), C.c_int64(F), _p(off, C.c_int64), _p(uv, C.c_float),
-                                        _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                        C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                        _p(t, C.c_double), C.byref(s)))
+        obs = (uv_views, xyz_views, _p(counts, C.c_int64))
+    else:
+        obs = (_p(off, C.c_int64), _p(uv, C.c_float), _p(xyz, C.c_float))
+    _check(getattr(lib(), name)(C.byref(opt), C.c_int32(device), C.c_int64(F), *obs, _p(d5, C.c_double) if d5 is not None else None,
+                                C.c_uint32(const_mask), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                _p(t, C.c_double), C.byref(s), *tail))
     return K.reshape(3, 3), intr, q, t, _summary_dict(s, log)
 
 
@@ -720,37 +690,25 @@ def intrinsics_batch_estimate(problems, distortion5=None, const_mask=None, optio
     ss, logs = _batch_summaries(B, log_capacity)
     if start == "fisheye":
         so = start_options if isinstance(start_options, IntrStartOptions) else intr_start_options(**(start_options or {}))
-        ha = None
-        if huber_a is not None:
-            ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
-            assert ha.size == B
-        _check(lib().cc_intrinsics_batch_estimate_start(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
-                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                                        _p(t, C.c_double), ss, _p(ha, C.c_double) if ha is not None else None,
-                                                        C.c_int32(model), C.byref(so)))
-    elif model != 0:   # (0 is off: the symbols without a model argument, below; an unknown value goes on to the C side, which refuses it)
-        ha = None
-        if huber_a is not None:
-            ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
-            assert ha.size == B
-        _check(lib().cc_intrinsics_batch_estimate_model(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
-                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                                        _p(t, C.c_double), ss, _p(ha, C.c_double) if ha is not None else None,
-                                                        C.c_int32(model)))
-    elif huber_a is not None:
+    ha = None
+    if huber_a is not None:
         ha = _f64(np.asarray(huber_a, dtype=np.float64).reshape(-1))
         assert ha.size == B
-        _check(lib().cc_intrinsics_batch_estimate_huber(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
-                                                        _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                                        _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                                        _p(t, C.c_double), ss, _p(ha, C.c_double)))
+    ha_p = _p(ha, C.c_double) if ha is not None else None
+    # The symbol and what it takes behind the shared arguments. model 0 is off: the symbols without a model argument; an unknown
+    # value goes on to the C side, which refuses it.
+    if start == "fisheye":
+        name, tail = "cc_intrinsics_batch_estimate_start", (ha_p, C.c_int32(model), C.byref(so))
+    elif model != 0:
+        name, tail = "cc_intrinsics_batch_estimate_model", (ha_p, C.c_int32(model))
+    elif ha is not None:
+        name, tail = "cc_intrinsics_batch_estimate_huber", (ha_p,)
     else:
-        _check(lib().cc_intrinsics_batch_estimate(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
-                                                  _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
-                                                  _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
-                                                  _p(t, C.c_double), ss))
+        name, tail = "cc_intrinsics_batch_estimate", ()
+    _check(getattr(lib(), name)(C.byref(opt), C.c_int32(device), C.c_int64(B), _p(poff, C.c_int64), _p(foff, C.c_int64),
+                                _p(uv, C.c_float), _p(xyz, C.c_float), _p(d5, C.c_double) if d5 is not None else None,
+                                _p(mask, C.c_uint32), _p(K, C.c_float), _p(intr, C.c_double), _p(q, C.c_double),
+                                _p(t, C.c_double), ss, *tail))
     qs = [q[poff[p]:poff[p + 1]].copy() for p in range(B)]
     ts = [t[poff[p]:poff[p + 1]].copy() for p in range(B)]
     return K.reshape(B, 3, 3), intr, qs, ts, [_summary_dict(ss[p], logs[p]) for p in range(B)]
@@ -800,10 +758,7 @@ def rig_optimize_frames(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world
     cam_q, cam_t = _f64(cam_q).copy(), _f64(cam_t).copy()
     frame_q, frame_t = _f64(frame_q).copy(), _f64(frame_t).copy()
     opt = options if options is not None else default_options(max_iterations=1000)
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
+    s, log = _summary(log_capacity)
     _check(lib().cc_rig_optimize_frames(C.byref(opt), C.c_int32(device), C.c_int64(n_cams), C.c_int64(F),
                                         C.c_int64(world_xyz.size // 3), ptrs, _p(counts, C.c_int64), C.byref(lay),
                                         _p(world_xyz, C.c_float), _p(cam_q, C.c_double), _p(cam_t, C.c_double),
@@ -847,10 +802,7 @@ def rig_optimize_columns(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, worl
     cam_q, cam_t = _f64(cam_q).copy(), _f64(cam_t).copy()
     frame_q, frame_t = _f64(frame_q).copy(), _f64(frame_t).copy()
     opt = options if options is not None else default_options(max_iterations=1000)
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
+    s, log = _summary(log_capacity)
     _check(lib().cc_rig_optimize_columns(C.byref(opt), C.c_int32(device), C.c_int64(n_cams), C.c_int64(F),
                                          C.c_int64(world_xyz.size // 3), C.byref(oc), _p(counts, C.c_int64),
                                          _p(world_xyz, C.c_float), _p(cam_q, C.c_double), _p(cam_t, C.c_double),
@@ -964,10 +916,7 @@ class RigProblem:
 
     def solve(self, options=None, log_capacity=2048):
         opt = options if options is not None else default_options(max_iterations=1000)
-        log = (Iteration * max(1, log_capacity))()
-        s = Summary()
-        s.log = C.cast(log, C.POINTER(Iteration))
-        s.log_capacity = log_capacity
+        s, log = _summary(log_capacity)
         _check(lib().cc_rig_solve(self._h, C.byref(opt), C.byref(s)))
         return _summary_dict(s, log)
 
@@ -1104,10 +1053,7 @@ def rig_optimize(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, c
     frame_q, frame_t = _f64(frame_q).copy(), _f64(frame_t).copy()
     cost = np.zeros(len(obs_cam))
     opt = options if options is not None else default_options(max_iterations=1000)
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
+    s, log = _summary(log_capacity)
     if devices is not None:
         devs = np.ascontiguousarray(devices, dtype=np.int32)
         _check(lib().cc_rig_optimize_multi(C.byref(opt), C.c_int32(len(devs)), _p(devs, C.c_int32), C.c_int64(n_cams), C.c_int64(F),
@@ -1143,10 +1089,7 @@ def rig_estimate(n_cams, frame_offsets, obs_cam, obs_world, obs_uv, world_xyz, c
     frame_t = np.zeros((F, 3)) if frame_t is None else _f64(frame_t).copy()
     cost = np.zeros(len(obs_cam))
     opt = options if options is not None else default_options(max_iterations=1000)
-    log = (Iteration * max(1, log_capacity))()
-    s = Summary()
-    s.log = C.cast(log, C.POINTER(Iteration))
-    s.log_capacity = log_capacity
+    s, log = _summary(log_capacity)
     _check(lib().cc_rig_estimate(C.byref(opt), C.c_int32(device), C.c_int64(n_cams), C.c_int64(F),
                                  C.c_int64(world_xyz.size // 3), _p(off, C.c_int64), _p(obs_cam, C.c_uint32),
                                  _p(obs_world, C.c_uint64), _p(obs_uv, C.c_float), _p(world_xyz, C.c_float),

@@ -131,18 +131,16 @@ void Calibrator::Estimate(const std::vector<Points2D>& pixels_per_view, const st
     cc_options options;
     cc_options_init(&options);  // non-monotonic steps, 100 iterations: calibrator.cpp:314-321
     cc_summary summary{};
-    if (focal_search) {   // EXTENSION: the same call with the start chosen
-      cc_intr_start_options start;
-      cc_intr_start_options_init(&start);
+    // EXTENSION: the start is an argument of the one call (NULL: Zhang's, which is cc_intrinsics_estimate_views_model, and with
+    // model 0, RadTan, and no loss cc_intrinsics_estimate_views)
+    cc_intr_start_options start;
+    cc_intr_start_options_init(&start);
+    if (focal_search)
       for (float& v : K9) v = 0.0f;
-      last_status_ = cc_intrinsics_estimate_views_start(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
-                                                        dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_,
-                                                        static_cast<int32_t>(model_), &start);
-      last_start_focal_ = K9[0];
-    } else
-    last_status_ = cc_intrinsics_estimate_views_model(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
+    last_status_ = cc_intrinsics_estimate_views_start(&options, device_, (int64_t)n_img, uv_views.data(), xyz_views.data(), counts.data(),
                                                       dist5, frozen, K9, intr, qd.data(), td.data(), &summary, huber_a_,
-                                                      static_cast<int32_t>(model_));   // (0, RadTan: cc_intrinsics_estimate_views)
+                                                      static_cast<int32_t>(model_), focal_search ? &start : nullptr);
+    if (focal_search) last_start_focal_ = K9[0];
     cc_last_call_timing(&last_timing_ms_[1]);
     // Same contract as the two-step path below: environment errors (no device, HIP, exchange) and the Zhang
     // preconditions (cc_zhang_init's CC_ERR_BAD_ARGUMENT: < 3 frames, < 4 points in a frame) throw; a solver-level
@@ -271,17 +269,11 @@ void Calibrator::EstimateManyFrom(const std::vector<Calibrator*>& calibrators, c
   std::memset(summaries.data(), 0, B * sizeof(cc_summary));
   cc_intr_start_options start_options;
   cc_intr_start_options_init(&start_options);
-  const int rc = focal_search
-      ? cc_intrinsics_batch_estimate_start(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
-                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
-                                           any_huber ? huber.data() : nullptr, CC_MODEL_FISHEYE, &start_options)
-      : fisheye
-      ? cc_intrinsics_batch_estimate_model(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
-                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
-                                           any_huber ? huber.data() : nullptr, CC_MODEL_FISHEYE)
-      : cc_intrinsics_batch_estimate_huber(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
-                                           dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
-                                           any_huber ? huber.data() : nullptr);
+  // (a NULL start is cc_intrinsics_batch_estimate_model, and that with CC_MODEL_RADTAN cc_intrinsics_batch_estimate_huber)
+  const int rc = cc_intrinsics_batch_estimate_start(&options, calibrators[0]->device_, (int64_t)B, poff.data(), foff.data(), uv.data(), xyz.data(),
+                                                    dist5.data(), frozen.data(), K9.data(), intr.data(), qd.data(), td.data(), summaries.data(),
+                                                    any_huber ? huber.data() : nullptr, fisheye ? CC_MODEL_FISHEYE : CC_MODEL_RADTAN,
+                                                    focal_search ? &start_options : nullptr);
   for (size_t p = 0; p < B; ++p) calibrators[p]->last_status_ = rc;
   // the same contract as Estimate(): environment errors and the Zhang preconditions throw, a solver-level status does not
   if (rc == CC_ERR_NO_DEVICE || rc == CC_ERR_HIP || rc == CC_ERR_COMM || rc == CC_ERR_BAD_ARGUMENT)

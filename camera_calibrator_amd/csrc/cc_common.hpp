@@ -30,6 +30,13 @@ int fail(int code, const char* fmt, ...);
 
 int select_device(int device);
 
+// Lays pieces out in one block of memory (a handle's device arena, a scratch block), each at a 256-byte boundary: take() returns
+// the offset of the next piece, `bytes` is the size so far.
+struct ArenaCursor {
+  size_t bytes = 0;
+  size_t take(size_t b) { const size_t at = bytes; bytes += (b + 255) & ~(size_t)255; return at; }
+};
+
 // Small per-process caches of resources that are slow to create and destroy (hipHostMalloc/hipHostFree
 // ~0.2-0.4 ms, streams ~0.1 ms): a one-shot solve should not pay for them every time. Pinned blocks
 // are kPinnedBlockBytes (control block / options staging in the first 512, the intrinsics handle's tagged publication

@@ -1,6 +1,6 @@
 // cc_intr_start_batch_host.hpp -- the host side of the batched fisheye focal-length start (cc_intrinsics_batch_estimate_start_fisheye,
-// cc_intrinsics_batch_start_scores, cc_intrinsics_batch_estimate_start): a part of cc_intrinsics_batch.hip, included there once,
-// behind the handle, its helpers and the one-shot calls. The kernels: cc_intr_start_batch.hpp.
+// cc_intrinsics_batch_start_scores; intr_start_batch_run also serves the one-shot pipeline): a part of cc_intrinsics_batch.hip,
+// included there once, behind the handle and its helpers, ahead of the one-shot calls. The kernels: cc_intr_start_batch.hpp.
 #pragma once
 
 #include "cc_intr_start_batch.hpp"
@@ -14,17 +14,16 @@ namespace cc {
 struct IntrStartBatchLayout {
   size_t o_prob, o_where, o_extent, tables_bytes, o_box, o_ext, o_f, o_score, o_qual, o_best, o_srec, o_skind, o_view, o_kind, bytes;
   IntrStartBatchLayout(int64_t B, int64_t Ftot, int64_t Stot, int64_t E, int64_t C) {
-    size_t cursor = 0;
-    auto take = [&](size_t b) { const size_t at = cursor; cursor += (b + 255) & ~(size_t)255; return at; };
-    o_prob = take((size_t)B * sizeof(IntrStartDev)); o_where = take((size_t)Stot * 2 * sizeof(int32_t));
-    o_extent = take((size_t)E * sizeof(IntrStartExtentWg));
-    tables_bytes = cursor;
-    o_box = take((size_t)B * 8 * sizeof(unsigned long long)); o_ext = take((size_t)B * 4 * sizeof(double));
-    o_f = take((size_t)B * kIntrStartMaxCandidates * sizeof(double)); o_score = take((size_t)B * kIntrStartMaxCandidates * sizeof(double));
-    o_qual = take((size_t)B * kIntrStartMaxCandidates * sizeof(int32_t)); o_best = take((size_t)B * 2 * sizeof(int32_t));
-    o_srec = take((size_t)C * Stot * kRigViewStride * sizeof(double)); o_skind = take((size_t)C * Stot * sizeof(int32_t));
-    o_view = take((size_t)Ftot * kRigViewStride * sizeof(double)); o_kind = take((size_t)Ftot * sizeof(int32_t));
-    bytes = cursor;
+    ArenaCursor cur;
+    o_prob = cur.take((size_t)B * sizeof(IntrStartDev)); o_where = cur.take((size_t)Stot * 2 * sizeof(int32_t));
+    o_extent = cur.take((size_t)E * sizeof(IntrStartExtentWg));
+    tables_bytes = cur.bytes;
+    o_box = cur.take((size_t)B * 8 * sizeof(unsigned long long)); o_ext = cur.take((size_t)B * 4 * sizeof(double));
+    o_f = cur.take((size_t)B * kIntrStartMaxCandidates * sizeof(double)); o_score = cur.take((size_t)B * kIntrStartMaxCandidates * sizeof(double));
+    o_qual = cur.take((size_t)B * kIntrStartMaxCandidates * sizeof(int32_t)); o_best = cur.take((size_t)B * 2 * sizeof(int32_t));
+    o_srec = cur.take((size_t)C * Stot * kRigViewStride * sizeof(double)); o_skind = cur.take((size_t)C * Stot * sizeof(int32_t));
+    o_view = cur.take((size_t)Ftot * kRigViewStride * sizeof(double)); o_kind = cur.take((size_t)Ftot * sizeof(int32_t));
+    bytes = cur.bytes;
   }
 };
 
@@ -176,63 +175,6 @@ int cc_intrinsics_batch_start_scores(cc_intrinsics_batch* h, double* f, double* 
       if (qualified) qualified[p * C + j] = dq[p * M + j];
     }
   return CC_OK;
-}
-
-// cc_intrinsics_batch_estimate_model with the start chosen: NULL -> that call (Zhang); else the focal search on the fisheye model
-int cc_intrinsics_batch_estimate_start(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
-                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
-                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
-                                       const double* huber_a, int32_t model, const cc_intr_start_options* start) {
-  if (!start)
-    return cc_intrinsics_batch_estimate_model(opt, device, n_problems, problem_offsets, frame_offsets, uv, xyz, distortion5, const_mask,
-                                              K_init9, intr9, q, t, summaries, huber_a, model);
-  using namespace cc;
-  const char* who = "cc_intrinsics_batch_estimate_start";
-  if (!intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: intr9 / q / t are NULL", who);
-  if (huber_a)
-    for (int64_t p = 0; p < n_problems; ++p)
-      if (huber_a[p] != huber_a[p]) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a[%lld] is NaN", who, (long long)p);
-  if (model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: the focal-length search is a start of the fisheye model (model %d)", who, (int)model);
-  if (int rc = intr_start_check(*start, who)) return rc;
-  IntrStartBatchTables tables;
-  {   // the offsets, before any device call
-    std::vector<int32_t> first, where;
-    if (int rc = batch_build_tables(who, n_problems, problem_offsets, frame_offsets, &first, &where)) return rc;
-    for (int64_t p = 0; p < n_problems; ++p)
-      if (problem_offsets[p + 1] - problem_offsets[p] < 3) return fail(CC_ERR_BAD_ARGUMENT, "%s: problem %lld has fewer than 3 frames", who, (long long)p);
-    intr_start_batch_tables(n_problems, problem_offsets, frame_offsets, start->search_views, &tables);
-  }
-  const IntrStartBatchLayout L(n_problems, problem_offsets[n_problems], tables.searched[(size_t)n_problems], (int64_t)tables.extent.size(), start->candidates);
-  // (the scratch is a part of the one-shot arena: batch_create sizes its extra block per problem)
-  const size_t per_problem = (L.bytes + (size_t)n_problems - 1) / (size_t)n_problems;
-  cc_intrinsics_batch* h = nullptr;
-  if (int rc = batch_create(who, device, n_problems, problem_offsets, frame_offsets, uv, xyz, 0, per_problem, false, &h)) return rc;
-  struct Guard { cc_intrinsics_batch* h; ~Guard() { batch_destroy(h); } } guard{h};
-  h->model = model;   // (a fresh handle: no state yet)
-  IntrStartBatchOutcome outcome;
-  int rc = intr_start_batch_run(h, h->extra, tables, L, *start, who, intr9, q, t, nullptr, &outcome);   // (its wait covers the upload: uv / xyz are the caller's)
-  if (rc == CC_ERR_STATE) {   // (the data admit no start: the caller's arguments, not a state of a handle the caller has)
-    const std::string why = last_error();
-    rc = fail(CC_ERR_BAD_ARGUMENT, "%s", why.c_str());
-  }
-  if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
-  if (outcome.invalid_problem >= 0)
-    return fail(CC_ERR_BAD_ARGUMENT, "%s: problem %lld: view %lld has no pose at any candidate focal length (fewer than 4 points, collinear points, or a non-finite pixel or point)",
-                who, (long long)outcome.invalid_problem, (long long)outcome.invalid_view);
-  for (int64_t p = 0; p < n_problems; ++p) {
-    double* k = intr9 + p * 9;
-    if (K_init9) {
-      const float K9[9] = {(float)k[0], 0.0f, (float)k[2], 0.0f, (float)k[1], (float)k[3], 0.0f, 0.0f, 1.0f};
-      std::memcpy(K_init9 + p * 9, K9, sizeof(K9));
-    }
-    for (int i = 0; i < 4; ++i) k[4 + i] = distortion5 ? distortion5[p * 5 + i] : 0.0;   // the distortion starts from the caller's, as after Zhang
-    k[8] = 0.0;
-  }
-  rc = cc_intrinsics_batch_set_state(h, intr9, const_mask, q, t);
-  if (!rc && huber_a) rc = cc_intrinsics_batch_set_huber(h, huber_a);
-  if (!rc) rc = cc_intrinsics_batch_solve(h, opt, summaries);
-  if (!rc) rc = cc_intrinsics_batch_get_state(h, intr9, q, t);
-  return rc;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // cc_intr_start_host.hpp -- the host side of the fisheye focal-length start (cc_intrinsics_estimate_start_fisheye,
-// cc_intrinsics_start_scores, cc_intrinsics_estimate_views_start): a part of cc_intrinsics.hip, included there once, behind the
-// handle, its helpers and the one-shot calls. The kernels: cc_intr_start.hpp.
+// cc_intrinsics_start_scores; intr_start_run also serves the one-shot pipeline): a part of cc_intrinsics.hip, included there once,
+// behind the handle and its helpers, ahead of the one-shot calls. The kernels: cc_intr_start.hpp.
 #pragma once
 
 #include "cc_intr_start.hpp"
@@ -11,14 +11,13 @@ namespace cc {
 struct IntrStartLayout {
   size_t o_box, o_ext, o_f, o_score, o_qual, o_best, o_srec, o_skind, o_view, o_kind, bytes;
   IntrStartLayout(int64_t F, int64_t C, int64_t S) {
-    size_t cursor = 0;
-    auto take = [&](size_t b) { const size_t at = cursor; cursor += (b + 255) & ~(size_t)255; return at; };
-    o_box = take(8 * sizeof(unsigned long long)); o_ext = take(4 * sizeof(double));
-    o_f = take(kIntrStartMaxCandidates * sizeof(double)); o_score = take(kIntrStartMaxCandidates * sizeof(double));
-    o_qual = take(kIntrStartMaxCandidates * sizeof(int32_t)); o_best = take(2 * sizeof(int32_t));
-    o_srec = take((size_t)C * S * kRigViewStride * sizeof(double)); o_skind = take((size_t)C * S * sizeof(int32_t));
-    o_view = take((size_t)F * kRigViewStride * sizeof(double)); o_kind = take((size_t)F * sizeof(int32_t));
-    bytes = cursor;
+    ArenaCursor cur;
+    o_box = cur.take(8 * sizeof(unsigned long long)); o_ext = cur.take(4 * sizeof(double));
+    o_f = cur.take(kIntrStartMaxCandidates * sizeof(double)); o_score = cur.take(kIntrStartMaxCandidates * sizeof(double));
+    o_qual = cur.take(kIntrStartMaxCandidates * sizeof(int32_t)); o_best = cur.take(2 * sizeof(int32_t));
+    o_srec = cur.take((size_t)C * S * kRigViewStride * sizeof(double)); o_skind = cur.take((size_t)C * S * sizeof(int32_t));
+    o_view = cur.take((size_t)F * kRigViewStride * sizeof(double)); o_kind = cur.take((size_t)F * sizeof(int32_t));
+    bytes = cur.bytes;
   }
 };
 
@@ -155,56 +154,6 @@ int cc_intrinsics_start_scores(cc_intrinsics* h, double* f, double* score, int32
   if (score) CC_HIP(hipMemcpy(score, work + L.o_score, C * sizeof(double), hipMemcpyDeviceToHost));
   if (qualified) CC_HIP(hipMemcpy(qualified, work + L.o_qual, C * sizeof(int32_t), hipMemcpyDeviceToHost));
   return CC_OK;
-}
-
-// cc_intrinsics_estimate_views_model with the start chosen: NULL -> that call (Zhang); else the focal search on the fisheye model
-int cc_intrinsics_estimate_views_start(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a, int32_t model,
-                                       const cc_intr_start_options* start) {
-  if (!start)
-    return cc_intrinsics_estimate_views_model(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, huber_a, model);
-  cc::last_call_status_reset();
-  using namespace cc;
-  const char* who = "cc_intrinsics_estimate_views_start";
-  if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: needs >= 3 views and non-NULL arrays", who);
-  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a is NaN", who);
-  if (model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: the focal-length search is a start of the fisheye model (model %d)", who, (int)model);
-  if (int rc = intr_start_check(*start, who)) return rc;
-  if (int rc = select_device(device)) return rc;
-  const IntrStartLayout L(F, start->candidates, intr_start_searched(*start, F));
-  double* tm = last_timing();
-  for (int i = 0; i < 5; ++i) tm[i] = 0.0;
-  ViewsUpload up;
-  if (int rc = up.open(who, device, F, uv_views, xyz_views, counts, 0, L.bytes)) return rc;
-  if (huber_a > 0.0) up.h->huber_a = huber_a;
-  up.h->model = model;
-  auto t0 = std::chrono::steady_clock::now();
-  int64_t first_invalid = -1;
-  int rc = intr_start_run(up.h, up.h->extra, *start, who, intr9, q, t, nullptr, &first_invalid, false);
-  tm[2] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (rc == CC_ERR_STATE) {   // (the data admit no start: the caller's arguments, not a state of a handle the caller has)
-    const std::string why = last_error();
-    rc = fail(CC_ERR_BAD_ARGUMENT, "%s", why.c_str());
-  }
-  if (!rc && first_invalid >= 0) rc = fail(CC_ERR_BAD_ARGUMENT, "%s: view %lld has no pose at any candidate focal length (fewer than 4 points, collinear points, or a non-finite pixel or point)", who, (long long)first_invalid);
-  if (!rc) {
-    if (K_init9) {
-      const float K9[9] = {(float)intr9[0], 0.0f, (float)intr9[2], 0.0f, (float)intr9[1], (float)intr9[3], 0.0f, 0.0f, 1.0f};
-      std::memcpy(K_init9, K9, sizeof(K9));
-    }
-    for (int i = 0; i < 4; ++i) intr9[4 + i] = distortion5 ? distortion5[i] : 0.0;   // the distortion starts from the caller's, as after Zhang
-    rc = cc_intrinsics_set_state(up.h, intr9, mask, q, t);
-  }
-  cc_options o;
-  if (opt) o = *opt; else cc_options_init(&o);
-  o.use_graph = 0;
-  if (!rc) rc = cc_intrinsics_solve(up.h, &o, summary);
-  tm[3] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (!rc) rc = cc_intrinsics_get_state(up.h, intr9, q, t);
-  tm[4] = ms_since(t0);
-  if (rc) (void)hipStreamSynchronize(up.h->stream);   // (an early return may have left copies from the staging block in flight)
-  return rc;
 }
 
 }  // extern "C"

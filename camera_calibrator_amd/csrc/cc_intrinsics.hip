@@ -943,10 +943,7 @@ struct cc_intrinsics : cc::SolveHost {   // pinned: a cached block, host_pub (16
   int elim_blocks = 1;
   void* arena = nullptr;        // every device buffer of the handle lives in this one allocation (cc::arena_get: cached between handles)
   bool arena_cached = false;
-  size_t extra_bytes = 0;       // set before creation: scratch appended to the arena (cc_intrinsics_estimate's initialisation)
-  char* extra = nullptr;
-  bool one_shot = false;        // the creator keeps uv / xyz alive until it has synchronised: no wait at the end of create
-  bool no_obs_upload = false;   // ... and uploads the observations itself
+  char* extra = nullptr;        // scratch behind the handle's own buffers in the arena (IntrCreate::extra_bytes: a one-shot call's start)
   double* init_intr = nullptr;  // [16]
   double* init_pose = nullptr;  // [F][8]
   bool have_state = false;
@@ -1066,26 +1063,17 @@ static int wait_solve(cc_intrinsics* h, LmCtl* c) {
 }  // namespace cc
 
 namespace cc {
-int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, const float* xyz);
-// (how the one-shot entry points -- cc_intrinsics_optimize / _estimate -- ask cc_intrinsics_create for a handle of their own
-// kind: the upload is not waited for, `extra` bytes of scratch ride in the same arena)
-static thread_local bool g_create_one_shot = false;
-static thread_local bool g_create_no_obs = false;   // the creator uploads uv / xyz itself (in pieces, as it packs them)
-static thread_local size_t g_create_extra = 0;
-struct OneShotCreate {
-  OneShotCreate(size_t extra, bool no_obs = false) { g_create_one_shot = true; g_create_extra = extra; g_create_no_obs = no_obs; }
-  ~OneShotCreate() { g_create_one_shot = false; g_create_extra = 0; g_create_no_obs = false; }
-};
 static double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-}
 
-extern "C" {
+// What a one-shot entry point asks of the handle it makes for itself (cc_intrinsics_create: the defaults)
+struct IntrCreate {
+  bool one_shot = false;        // the upload is not waited for: the creator keeps uv / xyz alive until it has synchronised
+  bool no_obs_upload = false;   // ... and uploads the observations itself (in pieces, as it packs them): uv / xyz may be NULL
+  size_t extra_bytes = 0;       // scratch behind the handle's buffers, in the same arena (h->extra)
+};
+int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, const float* xyz, const IntrCreate& how);
 
-void cc_intrinsics_destroy(cc_intrinsics* h);
-
-int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const float* uv,
-                         const float* xyz, cc_intrinsics** out) {
-  using namespace cc;
+static int intr_create(int32_t device, int64_t F, const int64_t* off, const float* uv, const float* xyz, const IntrCreate& how, cc_intrinsics** out) {
   if (!out || !off || F <= 0) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_create: bad arguments");
   if (off[0] != 0) return fail(CC_ERR_BAD_ARGUMENT, "frame_offsets[0] must be 0");
   for (int64_t f = 0; f < F; ++f)
@@ -1093,20 +1081,25 @@ int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const fl
   const int64_t N = off[F];
   if (F >= ((int64_t)1 << 28) || N >= ((int64_t)1 << 40))   // launch grids are 32-bit (F * tiles workgroups)
     return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_create: problem too large (frames < 2^28, observations < 2^40)");
-  if (N > 0 && (!uv || !xyz) && !cc::g_create_no_obs) return fail(CC_ERR_BAD_ARGUMENT, "uv/xyz are NULL");
+  if (N > 0 && (!uv || !xyz) && !how.no_obs_upload) return fail(CC_ERR_BAD_ARGUMENT, "uv/xyz are NULL");
   if (int rc = select_device(device)) return rc;
   cc_intrinsics* h = new cc_intrinsics();
   h->device = device; h->F = F; h->N = N;
-  h->one_shot = cc::g_create_one_shot;
-  h->no_obs_upload = cc::g_create_no_obs;
-  h->extra_bytes = cc::g_create_extra;
-  const int rc_init = cc::intr_create_impl(h, off, uv, xyz);
+  const int rc_init = intr_create_impl(h, off, uv, xyz, how);
   if (rc_init != CC_OK) {  // release whatever was allocated before the failure
     cc_intrinsics_destroy(h);
     return rc_init;
   }
   *out = h;
   return CC_OK;
+}
+}
+
+extern "C" {
+
+int cc_intrinsics_create(int32_t device, int64_t F, const int64_t* off, const float* uv,
+                         const float* xyz, cc_intrinsics** out) {
+  return cc::intr_create(device, F, off, uv, xyz, cc::IntrCreate{}, out);
 }
 
 int cc_intrinsics_exchange_export(cc_intrinsics* h, uint8_t handle[64]) {
@@ -1167,7 +1160,7 @@ int cc_intrinsics_exchange_attach(cc_intrinsics* h, int32_t rank, int32_t nranks
 }  // extern "C"
 
 namespace cc {
-int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, const float* xyz) {
+int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, const float* xyz, const IntrCreate& how) {
   const int64_t F = h->F, N = h->N;
   if (int rc = stream_get(h->device, &h->stream)) return rc;
   IntrDev& d = h->d;
@@ -1192,26 +1185,25 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   // one hipMalloc / hipMemset / hipFree instead of two dozen of each (destroy: 1.3 ms -> 0.1 ms).
   // Layout: [zero-initialised state | observations], 256-byte aligned pieces.
   const size_t n1 = (size_t)std::max<int64_t>(N, 1);
-  size_t cursor = 0;
-  auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
+  ArenaCursor cur;
   d.log_cap = 4096;
-  const size_t o_intr = take(2 * 16 * sizeof(double));
-  const size_t o_pose = take((size_t)2 * F * 8 * sizeof(double));
-  const size_t o_stats = take(FT * kStatsCols * sizeof(double));
-  const size_t o_hd0 = take(FT * 16 * sizeof(double));
-  const size_t o_sp = take((size_t)F * 8 * sizeof(double));
-  const size_t o_Y = take((size_t)F * kYStride * sizeof(double));
-  const size_t o_partial = take((size_t)kElimMaxBlocks * kPartialCols * sizeof(double));
-  const size_t o_vs = take(kVecSolve * sizeof(double));
-  const size_t o_vd = take(16 * sizeof(double));
-  const size_t o_ds = take(16 * sizeof(double));
-  const size_t o_ss = take(16 * sizeof(double));
-  const size_t o_ctl = take(sizeof(LmCtl));
-  const size_t o_ctln = take(sizeof(LmCtl));
-  const size_t o_sync = take(64);                     // arrival counter (+0), published-chunk counter (+8), final-sweep counts of the last persistent solve (+16, +20)
-  const size_t o_opts = take(sizeof(LmOpts));
-  const size_t o_iintr = take(16 * sizeof(double));
-  const size_t o_ipose = take((size_t)F * 8 * sizeof(double));
+  const size_t o_intr = cur.take(2 * 16 * sizeof(double));
+  const size_t o_pose = cur.take((size_t)2 * F * 8 * sizeof(double));
+  const size_t o_stats = cur.take(FT * kStatsCols * sizeof(double));
+  const size_t o_hd0 = cur.take(FT * 16 * sizeof(double));
+  const size_t o_sp = cur.take((size_t)F * 8 * sizeof(double));
+  const size_t o_Y = cur.take((size_t)F * kYStride * sizeof(double));
+  const size_t o_partial = cur.take((size_t)kElimMaxBlocks * kPartialCols * sizeof(double));
+  const size_t o_vs = cur.take(kVecSolve * sizeof(double));
+  const size_t o_vd = cur.take(16 * sizeof(double));
+  const size_t o_ds = cur.take(16 * sizeof(double));
+  const size_t o_ss = cur.take(16 * sizeof(double));
+  const size_t o_ctl = cur.take(sizeof(LmCtl));
+  const size_t o_ctln = cur.take(sizeof(LmCtl));
+  const size_t o_sync = cur.take(64);                     // arrival counter (+0), published-chunk counter (+8), final-sweep counts of the last persistent solve (+16, +20)
+  const size_t o_opts = cur.take(sizeof(LmOpts));
+  const size_t o_iintr = cur.take(16 * sizeof(double));
+  const size_t o_ipose = cur.take((size_t)F * 8 * sizeof(double));
   // persistent kernel: frames per worker workgroup = the fewest (1, 2, 4) that still gives every frame a team of a resident
   // workgroup -- few frames spread over the chip (a 125-frame shard: one frame per compute unit), many share them four
   // to a unit; seam mailboxes: one statistics row and one elimination row per worker workgroup, one row of column totals
@@ -1233,31 +1225,31 @@ int intr_create_impl(cc_intrinsics* h, const int64_t* off, const float* uv, cons
   }
   const int64_t PG = p_teams ? (F + p_teams - 1) / p_teams : 1;
   const size_t pgn = (size_t)PG;
-  const size_t o_pbox0 = cursor;
-  const size_t o_sbox = take(pgn * 2 * kPStatCols * sizeof(unsigned long long));
-  const size_t o_pbox = take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
-  const size_t o_rbox = take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
-  const size_t o_lbox = take((size_t)2 * kPartialCols * sizeof(unsigned long long));
-  const size_t o_xbox = take(kPBcastWords * sizeof(unsigned long long));
-  const size_t o_pfail = take(64);
-  h->p_box_bytes = cursor - o_pbox0;
-  const size_t zeroed = cursor;                       // everything above starts as zeros
-  const size_t o_blocks = take((size_t)2 * FT * 256 * sizeof(double));
-  const size_t o_log = take((size_t)d.log_cap * sizeof(cc_iteration));
-  const size_t o_uv = take(n1 * 2 * sizeof(float));
-  const size_t o_xyz = take(n1 * 3 * sizeof(float));
-  const size_t o_off = take((size_t)(F + 1) * sizeof(int64_t));
-  const size_t o_extra = take(h->extra_bytes);
-  if (int rc = arena_get(h->device, cursor, &h->arena, &h->arena_cached)) return rc;
+  const size_t o_pbox0 = cur.bytes;
+  const size_t o_sbox = cur.take(pgn * 2 * kPStatCols * sizeof(unsigned long long));
+  const size_t o_pbox = cur.take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
+  const size_t o_rbox = cur.take(pgn * 2 * kPartialCols * sizeof(unsigned long long));
+  const size_t o_lbox = cur.take((size_t)2 * kPartialCols * sizeof(unsigned long long));
+  const size_t o_xbox = cur.take(kPBcastWords * sizeof(unsigned long long));
+  const size_t o_pfail = cur.take(64);
+  h->p_box_bytes = cur.bytes - o_pbox0;
+  const size_t zeroed = cur.bytes;                       // everything above starts as zeros
+  const size_t o_blocks = cur.take((size_t)2 * FT * 256 * sizeof(double));
+  const size_t o_log = cur.take((size_t)d.log_cap * sizeof(cc_iteration));
+  const size_t o_uv = cur.take(n1 * 2 * sizeof(float));
+  const size_t o_xyz = cur.take(n1 * 3 * sizeof(float));
+  const size_t o_off = cur.take((size_t)(F + 1) * sizeof(int64_t));
+  const size_t o_extra = cur.take(how.extra_bytes);
+  if (int rc = arena_get(h->device, cur.bytes, &h->arena, &h->arena_cached)) return rc;
   char* base = static_cast<char*>(h->arena);
-  h->extra = h->extra_bytes ? base + o_extra : nullptr;
+  h->extra = how.extra_bytes ? base + o_extra : nullptr;
   CC_HIP(hipMemsetAsync(base, 0, zeroed, h->stream));
-  if (N > 0 && !h->no_obs_upload) {
+  if (N > 0 && !how.no_obs_upload) {
     CC_HIP(hipMemcpyAsync(base + o_uv, uv, (size_t)N * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
     CC_HIP(hipMemcpyAsync(base + o_xyz, xyz, (size_t)N * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
   }
   CC_HIP(hipMemcpyAsync(base + o_off, off, (size_t)(F + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (!h->one_shot) CC_HIP(hipStreamSynchronize(h->stream));            // the caller's arrays may go away after create
+  if (!how.one_shot) CC_HIP(hipStreamSynchronize(h->stream));            // the caller's arrays may go away after create
   d.uv = reinterpret_cast<const float*>(base + o_uv);
   d.xyz = reinterpret_cast<const float*>(base + o_xyz);
   d.off = reinterpret_cast<const int64_t*>(base + o_off);
@@ -1775,9 +1767,7 @@ int cc_intrinsics_optimize_multi(const cc_options* opt, int32_t n_devices, const
       if (!rc) { h->d.rank = r; h->d.nranks = n; h->exchange = true; }
     }
   }
-  cc_options o;
-  if (opt) o = *opt; else cc_options_init(&o);
-  o.use_graph = 0;   // one solve per handle: capturing and instantiating a graph cannot pay off
+  const cc_options o = one_shot_options(opt);
   std::vector<SolveRun> runs((size_t)n);
   for (int r = 0; r < n && !rc; ++r) rc = solve_begin(hs[(size_t)r], &o, &runs[(size_t)r]);
   // the persistent form, when EVERY shard fits it next to the shards that share its device (all in this process: no
@@ -1953,267 +1943,6 @@ int cc_intrinsics_profile_kernel(cc_intrinsics* h, int32_t which, int32_t n, dou
   return CC_OK;
 }
 
-int cc_intrinsics_optimize(const cc_options* opt, int32_t device, int64_t F, const int64_t* off,
-                           const float* uv, const float* xyz, double* intr9, uint32_t mask,
-                           double* q, double* t, cc_summary* summary) {
-  cc::last_call_status_reset();
-  cc_intrinsics* h = nullptr;
-  double* tm = cc::last_timing();
-  for (int i = 0; i < 5; ++i) tm[i] = 0.0;
-  auto t0 = std::chrono::steady_clock::now();
-  int rc;
-  { cc::OneShotCreate os(0); rc = cc_intrinsics_create(device, F, off, uv, xyz, &h); }
-  if (rc) return rc;
-  tm[0] = cc::ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (hipStreamSynchronize(h->stream) != hipSuccess) { (void)hipGetLastError(); rc = cc::fail(CC_ERR_HIP, "upload failed"); }   // (uv / xyz are the caller's)
-  tm[1] = cc::ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (!rc) rc = cc_intrinsics_set_state(h, intr9, mask, q, t);
-  cc_options o;
-  if (opt) o = *opt; else cc_options_init(&o);
-  o.use_graph = 0;   // one solve per handle: capturing and instantiating a graph cannot pay off
-  if (!rc) rc = cc_intrinsics_solve(h, &o, summary);
-  tm[3] = cc::ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (!rc) rc = cc_intrinsics_get_state(h, intr9, q, t);
-  cc_intrinsics_destroy(h);
-  tm[4] = cc::ms_since(t0);
-  return rc;
-}
-
-// Calibrator::Estimate in ONE call: the observations are uploaded once, Zhang's closed-form initialisation
-// (calibrator.cpp:47-66) runs on the handle's own device arrays, its K and poses -- rounded to float exactly as the
-// two-step path cc_zhang_init -> cc_intrinsics_optimize hands them over -- start the solve. Same results as the two
-// calls, one 20-byte-per-observation upload, one allocation and one pair of host packing loops less.
-namespace cc {
-// scratch of the Zhang initialisation, appended to the handle's arena: gram double[F][256] | H float[9F] | K float[9] | q float[4F] | t float[3F]
-struct ZhangScratch {
-  size_t o_gram, o_H, o_K, o_q, o_t, bytes;
-  explicit ZhangScratch(int64_t F) {
-    size_t cursor = 0;
-    auto take = [&](size_t b) { const size_t at = cursor; cursor += (b + 255) & ~(size_t)255; return at; };
-    o_gram = take((size_t)F * 256 * sizeof(double)); o_H = take((size_t)F * 9 * sizeof(float)); o_K = take(9 * sizeof(float));
-    o_q = take((size_t)F * 4 * sizeof(float)); o_t = take((size_t)F * 3 * sizeof(float));
-    bytes = cursor;
-  }
-};
-// Everything of cc_intrinsics_estimate behind the handle and its upload (enqueued on h->stream, not waited for): Zhang on the
-// device arrays, its K and poses rounded to float as the two-call path hands them over, the solve, the read-back.
-static int estimate_on_handle(cc_intrinsics* h, const ZhangScratch& zs, const cc_options* opt, int64_t F, const double* distortion5, uint32_t mask,
-                              float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, std::chrono::steady_clock::time_point t0) {
-  double* tm = last_timing();
-  char* sc = h->extra;
-  float* dK = reinterpret_cast<float*>(sc + zs.o_K);
-  float* dq = reinterpret_cast<float*>(sc + zs.o_q);
-  float* dt = reinterpret_cast<float*>(sc + zs.o_t);
-  // (the initialisation's kernels are enqueued behind the upload; the wait below covers both -- the split of the two in
-  // cc_last_call_timing comes from an event between them)
-  hipEvent_t ev_up = nullptr;
-  if (hipEventCreate(&ev_up) == hipSuccess) (void)hipEventRecord(ev_up, h->stream); else { ev_up = nullptr; (void)hipGetLastError(); }
-  int rc;
-  if ((rc = zhang_on_device(h->stream, F, h->d.off, h->d.uv, h->d.xyz, reinterpret_cast<double*>(sc + zs.o_gram),
-                            reinterpret_cast<float*>(sc + zs.o_H), dK, dq, dt))) {
-    if (ev_up) hipEventDestroy(ev_up);
-    return rc;
-  }
-  float K9[9];
-  std::vector<float> qf((size_t)F * 4), tf((size_t)F * 3);
-  CC_HIP(hipMemcpyAsync(K9, dK, sizeof(K9), hipMemcpyDeviceToHost, h->stream));
-  CC_HIP(hipMemcpyAsync(qf.data(), dq, qf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  CC_HIP(hipMemcpyAsync(tf.data(), dt, tf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  if (ev_up) {
-    (void)hipEventSynchronize(ev_up);
-    tm[1] += ms_since(t0); t0 = std::chrono::steady_clock::now();
-    hipEventDestroy(ev_up);
-  }
-  CC_HIP(hipStreamSynchronize(h->stream));
-  tm[2] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (K_init9) std::memcpy(K_init9, K9, sizeof(K9));
-  // intrinsics order fx fy px py k1 k2 p1 p2 k3 (calibrator.cpp:168-179); the distortion starts from the caller's
-  intr9[0] = K9[0]; intr9[1] = K9[4]; intr9[2] = K9[2]; intr9[3] = K9[5];
-  const int n_dist = h->model == CC_MODEL_FISHEYE ? 4 : 5;   // (fisheye: k1..k4, slot 8 unused)
-  for (int i = 0; i < 5; ++i) intr9[4 + i] = distortion5 && i < n_dist ? distortion5[i] : 0.0;
-  for (size_t i = 0; i < qf.size(); ++i) q[i] = qf[i];
-  for (size_t i = 0; i < tf.size(); ++i) t[i] = tf[i];
-  if ((rc = cc_intrinsics_set_state(h, intr9, mask, q, t))) return rc;
-  cc_options o;
-  if (opt) o = *opt; else cc_options_init(&o);
-  o.use_graph = 0;   // one solve per handle: capturing and instantiating a graph cannot pay off
-  if ((rc = cc_intrinsics_solve(h, &o, summary))) return rc;
-  tm[3] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  rc = cc_intrinsics_get_state(h, intr9, q, t);
-  tm[4] = ms_since(t0);   // (+ the handle's teardown, a few microseconds with the cached arena, after this function returns)
-  return rc;
-}
-}  // namespace cc
-
-int cc_intrinsics_estimate(const cc_options* opt, int32_t device, int64_t F, const int64_t* off, const float* uv,
-                           const float* xyz, const double* distortion5, uint32_t mask, float* K_init9, double* intr9,
-                           double* q, double* t, cc_summary* summary) {
-  cc::last_call_status_reset();
-  using namespace cc;
-  if (F < 3 || !off || !uv || !xyz || !intr9 || !q || !t)
-    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate: needs >= 3 frames and non-NULL arrays");
-  for (int64_t f = 0; f < F; ++f)
-    if (off[f + 1] - off[f] < 4) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate: frame %lld has fewer than 4 points", (long long)f);
-  const ZhangScratch zs(F);
-  double* tm = last_timing();
-  for (int i = 0; i < 5; ++i) tm[i] = 0.0;
-  auto t0 = std::chrono::steady_clock::now();
-  cc_intrinsics* h = nullptr;
-  int rc;
-  { OneShotCreate os(zs.bytes); rc = cc_intrinsics_create(device, F, off, uv, xyz, &h); }
-  if (rc) return rc;
-  struct Guard { cc_intrinsics* h; ~Guard() { cc_intrinsics_destroy(h); } } guard{h};
-  tm[0] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  return estimate_on_handle(h, zs, opt, F, distortion5, mask, K_init9, intr9, q, t, summary, t0);
-}
-
-// The same for a caller whose views are separate arrays (the reference's vector<Points2D> / vector<Points3D> arguments,
-// calibrator.cpp:47-68): view i has counts[i] points at uv_views[i] (2 floats each) and xyz_views[i] (3 floats each). The
-// library packs them into its cached pinned staging block IN PIECES and uploads every piece as soon as it is packed: the
-// copy of piece k over PCIe runs under the packing of piece k + 1, and the first kernels behind the last one.
-namespace cc {
-struct ViewsUpload {
-  void* staging = nullptr;
-  cc_intrinsics* h = nullptr;
-  ~ViewsUpload() { if (h) cc_intrinsics_destroy(h); staging_put(staging); }   // (the handle's stream is idle by then: every path below waits on it)
-  int open(const char* who, int32_t device, int64_t F, const float* const* uv_views, const float* const* xyz_views,
-           const int64_t* counts, int64_t min_points, size_t extra_bytes) {
-    int64_t N = 0;
-    for (int64_t f = 0; f < F; ++f) {
-      if (counts[f] < min_points || (counts[f] > 0 && (!uv_views[f] || !xyz_views[f])))
-        return fail(CC_ERR_BAD_ARGUMENT, "%s: view %lld has %lld points (needs >= %lld, non-NULL)", who, (long long)f, (long long)counts[f], (long long)min_points);
-      N += counts[f];
-    }
-    double* tm = last_timing();
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t b_off = ((size_t)(F + 1) * sizeof(int64_t) + 255) & ~(size_t)255, b_uv = ((size_t)N * 2 * sizeof(float) + 255) & ~(size_t)255;
-    bool st_cached = false;
-    staging = staging_get(b_off + b_uv + (size_t)N * 3 * sizeof(float) + 256, &st_cached);
-    if (!staging) return fail(CC_ERR_HIP, "%s: pinned staging memory could not be allocated", who);
-    char* st = static_cast<char*>(staging);
-    int64_t* off = reinterpret_cast<int64_t*>(st);
-    float* uv = reinterpret_cast<float*>(st + b_off);
-    float* xyz = reinterpret_cast<float*>(st + b_off + b_uv);
-    off[0] = 0;
-    for (int64_t f = 0; f < F; ++f) off[f + 1] = off[f] + counts[f];
-    int rc;
-    { OneShotCreate os(extra_bytes, true); rc = cc_intrinsics_create(device, F, off, nullptr, nullptr, &h); }
-    if (rc) return rc;
-    tm[0] = ms_since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
-    // THREE pieces of a large problem (none below 32k observations = 640 KB): every hipMemcpyAsync costs about 7.5 us of host
-    // time and the link moves ~36 GB/s either way, so more pieces lose what the overlap gains (measured at 500k observations,
-    // pack + upload: 1 piece 0.47-0.49 ms, 2: 0.39-0.40, 3: 0.38-0.39, 4: 0.45, 8: 0.51, 32: 0.92; a second stream for xyz
-    // or a kernel that pulls the pinned block over PCIe itself made no difference beyond box-to-box noise)
-    const int64_t piece = std::max<int64_t>(32768, N / 3 + 1);
-    float* duv = const_cast<float*>(h->d.uv);
-    float* dxyz = const_cast<float*>(h->d.xyz);
-    int64_t f0 = 0;
-    while (f0 < F) {
-      int64_t f1 = f0;
-      while (f1 < F && off[f1] - off[f0] < piece) ++f1;
-      for (int64_t f = f0; f < f1; ++f) {
-        if (!counts[f]) continue;
-        std::memcpy(uv + 2 * off[f], uv_views[f], (size_t)counts[f] * 2 * sizeof(float));
-        std::memcpy(xyz + 3 * off[f], xyz_views[f], (size_t)counts[f] * 3 * sizeof(float));
-      }
-      const size_t n = (size_t)(off[f1] - off[f0]);
-      if (n) {
-        CC_HIP(hipMemcpyAsync(duv + 2 * off[f0], uv + 2 * off[f0], n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        CC_HIP(hipMemcpyAsync(dxyz + 3 * off[f0], xyz + 3 * off[f0], n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
-      }
-      f0 = f1;
-    }
-    tm[1] = ms_since(t1);   // packing + enqueueing; the callers add their wait for the last piece
-    return CC_OK;
-  }
-};
-}  // namespace cc
-
-// (cc_intrinsics_estimate_views is this with huber_a = 0 and model 0: the same path, bit for bit. With the fisheye model the
-// start is still Zhang's pinhole one with k = 0, and `distortion5` holds the model's four coefficients.)
-int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
-  cc::last_call_status_reset();
-  using namespace cc;
-  if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
-    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views: needs >= 3 views and non-NULL arrays");
-  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_huber: huber_a is NaN");
-  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_model: unknown model %d", (int)model);
-  if (model != CC_MODEL_RADTAN)   // (a missing device is reported as such, ahead of the pinned staging block that needs one)
-    if (int rc = select_device(device)) return rc;
-  const ZhangScratch zs(F);
-  double* tm = last_timing();
-  for (int i = 0; i < 5; ++i) tm[i] = 0.0;
-  ViewsUpload up;
-  if (int rc = up.open("cc_intrinsics_estimate_views", device, F, uv_views, xyz_views, counts, 4, zs.bytes)) return rc;
-  if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
-  up.h->model = model;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = estimate_on_handle(up.h, zs, opt, F, distortion5, mask, K_init9, intr9, q, t, summary, t0);
-  if (rc) (void)hipStreamSynchronize(up.h->stream);   // (an early return may have left copies from the staging block in flight)
-  return rc;
-}
-
-int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a) {
-  return cc_intrinsics_estimate_views_model(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, huber_a, CC_MODEL_RADTAN);
-}
-
-int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                 const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
-                                 float* K_init9, double* intr9, double* q, double* t, cc_summary* summary) {
-  return cc_intrinsics_estimate_views_huber(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, 0.0);
-}
-
-// cc_intrinsics_optimize for views given as separate arrays (Calibrator::Optimize's arguments, calibrator.cpp:70-74).
-// (cc_intrinsics_optimize_views is this with huber_a = 0 and model 0: the same path, bit for bit)
-int cc_intrinsics_optimize_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
-                                       double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
-  cc::last_call_status_reset();
-  using namespace cc;
-  if (F < 1 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
-    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views: needs >= 1 view and non-NULL arrays");
-  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_huber: huber_a is NaN");
-  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_model: unknown model %d", (int)model);
-  if (model != CC_MODEL_RADTAN)   // (a missing device is reported as such, ahead of the pinned staging block that needs one)
-    if (int rc = select_device(device)) return rc;
-  double* tm = last_timing();
-  for (int i = 0; i < 5; ++i) tm[i] = 0.0;
-  ViewsUpload up;
-  if (int rc = up.open("cc_intrinsics_optimize_views", device, F, uv_views, xyz_views, counts, 0, 0)) return rc;
-  if (huber_a > 0.0) up.h->huber_a = huber_a;   // EXTENSION (a fresh handle: no graph, no exchange)
-  up.h->model = model;
-  auto t0 = std::chrono::steady_clock::now();
-  int rc = CC_OK;
-  if (hipStreamSynchronize(up.h->stream) != hipSuccess) { (void)hipGetLastError(); rc = fail(CC_ERR_HIP, "upload failed"); }
-  tm[1] += ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (!rc) rc = cc_intrinsics_set_state(up.h, intr9, mask, q, t);
-  cc_options o;
-  if (opt) o = *opt; else cc_options_init(&o);
-  o.use_graph = 0;
-  if (!rc) rc = cc_intrinsics_solve(up.h, &o, summary);
-  tm[3] = ms_since(t0); t0 = std::chrono::steady_clock::now();
-  if (!rc) rc = cc_intrinsics_get_state(up.h, intr9, q, t);
-  tm[4] = ms_since(t0);
-  return rc;
-}
-
-int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
-                                       double* q, double* t, cc_summary* summary, double huber_a) {
-  return cc_intrinsics_optimize_views_model(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, huber_a, CC_MODEL_RADTAN);
-}
-
-int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
-                                 const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
-                                 double* q, double* t, cc_summary* summary) {
-  return cc_intrinsics_optimize_views_huber(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, 0.0);
-}
-
 int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t rank, int32_t nranks) {
   using namespace cc;
   if (!h || !id || rank < 0 || nranks < 1 || rank >= nranks || nranks > 32)
@@ -2231,5 +1960,323 @@ int cc_intrinsics_comm_init(cc_intrinsics* h, const uint8_t id[128], int32_t ran
 
 }  // extern "C"
 
-// EXTENSION: the fisheye focal-length start (cc_intrinsics_estimate_start_fisheye and the one-shot call that takes a start)
+// EXTENSION: the fisheye focal-length start on a handle (cc_intrinsics_estimate_start_fisheye; the one-shot pipeline below runs it too)
 #include "cc_intr_start_host.hpp"
+
+// The one-shot calls (cc_intrinsics_optimize, cc_intrinsics_estimate and their _views / _huber / _model / _start forms): ONE
+// pipeline -- a handle of the one-shot kind, the upload, a start, set_state -> solve without a graph -> get_state, the phase
+// timings, the teardown -- and one filled-in IntrOneShot per entry point ("One-shot calls", has the table).
+namespace cc {
+
+// scratch of the Zhang initialisation, appended to the handle's arena: gram double[F][256] | H float[9F] | K float[9] | q float[4F] | t float[3F]
+struct ZhangScratch {
+  size_t o_gram, o_H, o_K, o_q, o_t, bytes;
+  explicit ZhangScratch(int64_t F) {
+    ArenaCursor cur;
+    o_gram = cur.take((size_t)F * 256 * sizeof(double)); o_H = cur.take((size_t)F * 9 * sizeof(float)); o_K = cur.take(9 * sizeof(float));
+    o_q = cur.take((size_t)F * 4 * sizeof(float)); o_t = cur.take((size_t)F * 3 * sizeof(float));
+    bytes = cur.bytes;
+  }
+};
+
+struct IntrOneShot {
+  const char* who;                // the call's name in the messages of the view checks, the staging block and the focal search
+  const cc_options* opt;
+  int32_t device;
+  int64_t F;
+  uint32_t mask;
+  double *intr9, *q, *t;          // CALLER: the start on entry; every start: the solution on return
+  cc_summary* summary;
+  // The observations: packed (off / uv / xyz, uploaded by the handle's creation), or one array per view (`counts` non-NULL), which
+  // the pipeline packs into pinned staging and uploads in pieces; every view then has at least min_points points.
+  const int64_t *off = nullptr, *counts = nullptr;
+  const float *uv = nullptr, *xyz = nullptr;
+  const float *const *uv_views = nullptr, *const *xyz_views = nullptr;
+  int64_t min_points = 0;
+  // The start: the caller's state; Zhang's closed form on the handle's device arrays, K and poses rounded to float exactly as the
+  // two calls cc_zhang_init -> cc_intrinsics_optimize hand them over; or the fisheye focal search (`search`, checked by the caller).
+  enum Start { CALLER, ZHANG, FOCAL_SEARCH } start = CALLER;
+  const cc_intr_start_options* search = nullptr;
+  const double* distortion5 = nullptr;   // ZHANG / FOCAL_SEARCH: where the distortion starts (NULL: zeros; fisheye: k1..k4, slot 8 unused)
+  float* K_init9 = nullptr;              // ... and where the start's K goes (may be NULL)
+  double huber_a = 0.0;                  // EXTENSION: > 0 -> HuberLoss(a)
+  int32_t model = CC_MODEL_RADTAN;       // EXTENSION
+};
+
+// the handle and the staging block of one call; the handle goes first: its destruction waits on its stream, so no copy from the
+// staging block is in flight when the block goes back to the cache
+struct OneShotOwned {
+  void* staging = nullptr;
+  cc_intrinsics* h = nullptr;
+  ~OneShotOwned() { if (h) cc_intrinsics_destroy(h); staging_put(staging); }
+};
+
+// Views given as separate arrays (the reference's vector<Points2D> / vector<Points3D> arguments, calibrator.cpp:47-74): view i has
+// counts[i] points at uv_views[i] (2 floats each) and xyz_views[i] (3 floats each). They are packed into the cached pinned staging
+// block IN PIECES and every piece is uploaded as soon as it is packed: the copy of piece k over PCIe runs under the packing of
+// piece k + 1, and the first kernels behind the last one. Nothing is waited for.
+static int one_shot_open_views(const IntrOneShot& a, size_t extra_bytes, OneShotOwned* own, PhaseClock* clock) {
+  const int64_t F = a.F;
+  int64_t N = 0;
+  for (int64_t f = 0; f < F; ++f) {
+    if (a.counts[f] < a.min_points || (a.counts[f] > 0 && (!a.uv_views[f] || !a.xyz_views[f])))
+      return fail(CC_ERR_BAD_ARGUMENT, "%s: view %lld has %lld points (needs >= %lld, non-NULL)", a.who, (long long)f, (long long)a.counts[f], (long long)a.min_points);
+    N += a.counts[f];
+  }
+  const size_t b_off = ((size_t)(F + 1) * sizeof(int64_t) + 255) & ~(size_t)255, b_uv = ((size_t)N * 2 * sizeof(float) + 255) & ~(size_t)255;
+  bool st_cached = false;
+  own->staging = staging_get(b_off + b_uv + (size_t)N * 3 * sizeof(float) + 256, &st_cached);
+  if (!own->staging) return fail(CC_ERR_HIP, "%s: pinned staging memory could not be allocated", a.who);
+  char* st = static_cast<char*>(own->staging);
+  int64_t* off = reinterpret_cast<int64_t*>(st);
+  float* uv = reinterpret_cast<float*>(st + b_off);
+  float* xyz = reinterpret_cast<float*>(st + b_off + b_uv);
+  off[0] = 0;
+  for (int64_t f = 0; f < F; ++f) off[f + 1] = off[f] + a.counts[f];
+  if (int rc = intr_create(a.device, F, off, nullptr, nullptr, IntrCreate{true, true, extra_bytes}, &own->h)) return rc;
+  cc_intrinsics* h = own->h;
+  clock->mark(0);
+  // THREE pieces of a large problem (none below 32k observations = 640 KB): every hipMemcpyAsync costs about 7.5 us of host
+  // time and the link moves ~36 GB/s either way, so more pieces lose what the overlap gains (measured at 500k observations,
+  // pack + upload: 1 piece 0.47-0.49 ms, 2: 0.39-0.40, 3: 0.38-0.39, 4: 0.45, 8: 0.51, 32: 0.92; a second stream for xyz
+  // or a kernel that pulls the pinned block over PCIe itself made no difference beyond box-to-box noise)
+  const int64_t piece = std::max<int64_t>(32768, N / 3 + 1);
+  float* duv = const_cast<float*>(h->d.uv);
+  float* dxyz = const_cast<float*>(h->d.xyz);
+  int64_t f0 = 0;
+  while (f0 < F) {
+    int64_t f1 = f0;
+    while (f1 < F && off[f1] - off[f0] < piece) ++f1;
+    for (int64_t f = f0; f < f1; ++f) {
+      if (!a.counts[f]) continue;
+      std::memcpy(uv + 2 * off[f], a.uv_views[f], (size_t)a.counts[f] * 2 * sizeof(float));
+      std::memcpy(xyz + 3 * off[f], a.xyz_views[f], (size_t)a.counts[f] * 3 * sizeof(float));
+    }
+    const size_t n = (size_t)(off[f1] - off[f0]);
+    if (n) {
+      CC_HIP(hipMemcpyAsync(duv + 2 * off[f0], uv + 2 * off[f0], n * 2 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      CC_HIP(hipMemcpyAsync(dxyz + 3 * off[f0], xyz + 3 * off[f0], n * 3 * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    }
+    f0 = f1;
+  }
+  clock->mark(1);   // packing + enqueueing; the start adds the wait for the last piece
+  return CC_OK;
+}
+
+// Zhang's closed form (calibrator.cpp:47-66) on the handle's own device arrays, enqueued behind the upload: K_init9, intr9[0..3],
+// q and t are its K and poses, rounded to float. One wait covers upload and initialisation; an event between the two splits it
+// into the upload's slot and the start's.
+static int one_shot_start_zhang(cc_intrinsics* h, const IntrOneShot& a, PhaseClock* clock) {
+  const int64_t F = a.F;
+  const ZhangScratch zs(F);
+  char* sc = h->extra;
+  float* dK = reinterpret_cast<float*>(sc + zs.o_K);
+  float* dq = reinterpret_cast<float*>(sc + zs.o_q);
+  float* dt = reinterpret_cast<float*>(sc + zs.o_t);
+  hipEvent_t ev_up = nullptr;
+  if (hipEventCreate(&ev_up) == hipSuccess) (void)hipEventRecord(ev_up, h->stream); else { ev_up = nullptr; (void)hipGetLastError(); }
+  if (int rc = zhang_on_device(h->stream, F, h->d.off, h->d.uv, h->d.xyz, reinterpret_cast<double*>(sc + zs.o_gram),
+                               reinterpret_cast<float*>(sc + zs.o_H), dK, dq, dt)) {
+    if (ev_up) hipEventDestroy(ev_up);
+    return rc;
+  }
+  float K9[9];
+  std::vector<float> qf((size_t)F * 4), tf((size_t)F * 3);
+  CC_HIP(hipMemcpyAsync(K9, dK, sizeof(K9), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipMemcpyAsync(qf.data(), dq, qf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipMemcpyAsync(tf.data(), dt, tf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (ev_up) {
+    (void)hipEventSynchronize(ev_up);
+    clock->mark(1);
+    hipEventDestroy(ev_up);
+  }
+  CC_HIP(hipStreamSynchronize(h->stream));
+  clock->mark(2);
+  if (a.K_init9) std::memcpy(a.K_init9, K9, sizeof(K9));
+  // intrinsics order fx fy px py k1 k2 p1 p2 k3 (calibrator.cpp:168-179)
+  a.intr9[0] = K9[0]; a.intr9[1] = K9[4]; a.intr9[2] = K9[2]; a.intr9[3] = K9[5];
+  for (size_t i = 0; i < qf.size(); ++i) a.q[i] = qf[i];
+  for (size_t i = 0; i < tf.size(); ++i) a.t[i] = tf[i];
+  return CC_OK;
+}
+
+// The fisheye focal search (cc_intr_start_host.hpp) in the arena's scratch: intr9[0..3], q and t are its pick, K_init9 that K. Its
+// one wait covers the upload, so the whole of it goes to the start's slot.
+static int one_shot_start_search(cc_intrinsics* h, const IntrOneShot& a, PhaseClock* clock) {
+  int64_t first_invalid = -1;
+  int rc = intr_start_run(h, h->extra, *a.search, a.who, a.intr9, a.q, a.t, nullptr, &first_invalid, false);
+  clock->mark(2);
+  if (rc == CC_ERR_STATE) {   // (the data admit no start: the caller's arguments, not a state of a handle the caller has)
+    const std::string why = last_error();
+    rc = fail(CC_ERR_BAD_ARGUMENT, "%s", why.c_str());
+  }
+  if (!rc && first_invalid >= 0)
+    rc = fail(CC_ERR_BAD_ARGUMENT, "%s: view %lld has no pose at any candidate focal length (fewer than 4 points, collinear points, or a non-finite pixel or point)", a.who, (long long)first_invalid);
+  if (!rc && a.K_init9) {
+    const float K9[9] = {(float)a.intr9[0], 0.0f, (float)a.intr9[2], 0.0f, (float)a.intr9[1], (float)a.intr9[3], 0.0f, 0.0f, 1.0f};
+    std::memcpy(a.K_init9, K9, sizeof(K9));
+  }
+  return rc;
+}
+
+static int one_shot_run(const IntrOneShot& a, OneShotOwned* own, PhaseClock* clock) {
+  size_t extra = 0;   // the start's scratch rides in the handle's arena
+  if (a.start == IntrOneShot::ZHANG) extra = ZhangScratch(a.F).bytes;
+  if (a.start == IntrOneShot::FOCAL_SEARCH) extra = IntrStartLayout(a.F, a.search->candidates, intr_start_searched(*a.search, a.F)).bytes;
+  if (a.counts) {
+    if (int rc = one_shot_open_views(a, extra, own, clock)) return rc;
+  } else {
+    if (int rc = intr_create(a.device, a.F, a.off, a.uv, a.xyz, IntrCreate{true, false, extra}, &own->h)) return rc;
+    clock->mark(0);
+  }
+  cc_intrinsics* h = own->h;
+  if (a.huber_a > 0.0) h->huber_a = a.huber_a;   // (a fresh handle: no graph, no exchange)
+  h->model = a.model;
+  if (a.start == IntrOneShot::CALLER) {
+    if (hipStreamSynchronize(h->stream) != hipSuccess) { (void)hipGetLastError(); return fail(CC_ERR_HIP, "upload failed"); }   // (uv / xyz are the caller's)
+    clock->mark(1);
+  } else {
+    if (int rc = a.start == IntrOneShot::ZHANG ? one_shot_start_zhang(h, a, clock) : one_shot_start_search(h, a, clock)) return rc;
+    const int n_dist = a.model == CC_MODEL_FISHEYE ? 4 : 5;   // the distortion starts from the caller's (fisheye: k1..k4, slot 8 unused)
+    for (int i = 0; i < 5; ++i) a.intr9[4 + i] = a.distortion5 && i < n_dist ? a.distortion5[i] : 0.0;
+  }
+  if (int rc = cc_intrinsics_set_state(h, a.intr9, a.mask, a.q, a.t)) return rc;
+  const cc_options o = one_shot_options(a.opt);
+  if (int rc = cc_intrinsics_solve(h, &o, a.summary)) return rc;
+  clock->mark(3);
+  return cc_intrinsics_get_state(h, a.intr9, a.q, a.t);
+}
+
+static int intr_one_shot(const IntrOneShot& a) {
+  // With a model other than CC_MODEL_RADTAN the device is selected ahead of everything else, so that a machine without one answers
+  // CC_ERR_NO_DEVICE. Kept as the symbols have it, because the return code differs: the radial-tangential calls are the older
+  // symbols, whose view checks win and whose missing device shows as the pinned staging block that could not be allocated
+  // (CC_ERR_HIP). With a device there is nothing to tell apart.
+  if (a.model != CC_MODEL_RADTAN)
+    if (int rc = select_device(a.device)) return rc;
+  PhaseClock clock;
+  int rc;
+  {
+    OneShotOwned own;
+    rc = one_shot_run(a, &own, &clock);
+    // (an early return may have left copies from the staging block in flight)
+    if (rc && own.h && own.staging) (void)hipStreamSynchronize(own.h->stream);
+  }
+  clock.mark(4);
+  return rc;
+}
+
+}  // namespace cc
+
+extern "C" {
+
+int cc_intrinsics_optimize(const cc_options* opt, int32_t device, int64_t F, const int64_t* off,
+                           const float* uv, const float* xyz, double* intr9, uint32_t mask,
+                           double* q, double* t, cc_summary* summary) {
+  cc::last_call_status_reset();
+  cc::IntrOneShot a{"cc_intrinsics_optimize", opt, device, F, mask, intr9, q, t, summary};
+  a.off = off; a.uv = uv; a.xyz = xyz;
+  return cc::intr_one_shot(a);
+}
+
+// Calibrator::Estimate in ONE call: the observations are uploaded once, Zhang's closed-form initialisation
+// (calibrator.cpp:47-66) runs on the handle's own device arrays, its K and poses -- rounded to float exactly as the
+// two-step path cc_zhang_init -> cc_intrinsics_optimize hands them over -- start the solve. Same results as the two
+// calls, one 20-byte-per-observation upload, one allocation and one pair of host packing loops less.
+int cc_intrinsics_estimate(const cc_options* opt, int32_t device, int64_t F, const int64_t* off, const float* uv,
+                           const float* xyz, const double* distortion5, uint32_t mask, float* K_init9, double* intr9,
+                           double* q, double* t, cc_summary* summary) {
+  cc::last_call_status_reset();
+  using namespace cc;
+  if (F < 3 || !off || !uv || !xyz || !intr9 || !q || !t)
+    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate: needs >= 3 frames and non-NULL arrays");
+  for (int64_t f = 0; f < F; ++f)
+    if (off[f + 1] - off[f] < 4) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate: frame %lld has fewer than 4 points", (long long)f);
+  IntrOneShot a{"cc_intrinsics_estimate", opt, device, F, mask, intr9, q, t, summary};
+  a.off = off; a.uv = uv; a.xyz = xyz;
+  a.start = IntrOneShot::ZHANG; a.distortion5 = distortion5; a.K_init9 = K_init9;
+  return intr_one_shot(a);
+}
+
+// The same for a caller whose views are separate arrays (one_shot_open_views).
+// (cc_intrinsics_estimate_views is this with huber_a = 0 and model 0: the same path, bit for bit. With the fisheye model the
+// start is still Zhang's pinhole one with k = 0, and `distortion5` holds the model's four coefficients.)
+int cc_intrinsics_estimate_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
+  cc::last_call_status_reset();
+  using namespace cc;
+  if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
+    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views: needs >= 3 views and non-NULL arrays");
+  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_huber: huber_a is NaN");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_estimate_views_model: unknown model %d", (int)model);
+  IntrOneShot a{"cc_intrinsics_estimate_views", opt, device, F, mask, intr9, q, t, summary};
+  a.uv_views = uv_views; a.xyz_views = xyz_views; a.counts = counts; a.min_points = 4;
+  a.start = IntrOneShot::ZHANG; a.distortion5 = distortion5; a.K_init9 = K_init9;
+  a.huber_a = huber_a; a.model = model;
+  return intr_one_shot(a);
+}
+
+int cc_intrinsics_estimate_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a) {
+  return cc_intrinsics_estimate_views_model(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, huber_a, CC_MODEL_RADTAN);
+}
+
+int cc_intrinsics_estimate_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                 const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                 float* K_init9, double* intr9, double* q, double* t, cc_summary* summary) {
+  return cc_intrinsics_estimate_views_huber(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, 0.0);
+}
+
+// EXTENSION: cc_intrinsics_estimate_views_model with the start chosen: NULL -> that call (Zhang); else the focal search on the fisheye model
+int cc_intrinsics_estimate_views_start(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, const double* distortion5, uint32_t mask,
+                                       float* K_init9, double* intr9, double* q, double* t, cc_summary* summary, double huber_a, int32_t model,
+                                       const cc_intr_start_options* start) {
+  if (!start)
+    return cc_intrinsics_estimate_views_model(opt, device, F, uv_views, xyz_views, counts, distortion5, mask, K_init9, intr9, q, t, summary, huber_a, model);
+  cc::last_call_status_reset();
+  using namespace cc;
+  const char* who = "cc_intrinsics_estimate_views_start";
+  if (F < 3 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: needs >= 3 views and non-NULL arrays", who);
+  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a is NaN", who);
+  if (model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: the focal-length search is a start of the fisheye model (model %d)", who, (int)model);
+  if (int rc = intr_start_check(*start, who)) return rc;
+  IntrOneShot a{who, opt, device, F, mask, intr9, q, t, summary};
+  a.uv_views = uv_views; a.xyz_views = xyz_views; a.counts = counts; a.min_points = 0;   // (a view the search cannot place is refused by name, behind the search)
+  a.start = IntrOneShot::FOCAL_SEARCH; a.search = start; a.distortion5 = distortion5; a.K_init9 = K_init9;
+  a.huber_a = huber_a; a.model = model;
+  return intr_one_shot(a);
+}
+
+// cc_intrinsics_optimize for views given as separate arrays (Calibrator::Optimize's arguments, calibrator.cpp:70-74).
+// (cc_intrinsics_optimize_views is this with huber_a = 0 and model 0: the same path, bit for bit)
+int cc_intrinsics_optimize_views_model(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                       double* q, double* t, cc_summary* summary, double huber_a, int32_t model) {
+  cc::last_call_status_reset();
+  using namespace cc;
+  if (F < 1 || !uv_views || !xyz_views || !counts || !intr9 || !q || !t)
+    return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views: needs >= 1 view and non-NULL arrays");
+  if (huber_a != huber_a) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_huber: huber_a is NaN");
+  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_optimize_views_model: unknown model %d", (int)model);
+  IntrOneShot a{"cc_intrinsics_optimize_views", opt, device, F, mask, intr9, q, t, summary};
+  a.uv_views = uv_views; a.xyz_views = xyz_views; a.counts = counts; a.min_points = 0;
+  a.huber_a = huber_a; a.model = model;
+  return intr_one_shot(a);
+}
+
+int cc_intrinsics_optimize_views_huber(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                       const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                       double* q, double* t, cc_summary* summary, double huber_a) {
+  return cc_intrinsics_optimize_views_model(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, huber_a, CC_MODEL_RADTAN);
+}
+
+int cc_intrinsics_optimize_views(const cc_options* opt, int32_t device, int64_t F, const float* const* uv_views,
+                                 const float* const* xyz_views, const int64_t* counts, double* intr9, uint32_t mask,
+                                 double* q, double* t, cc_summary* summary) {
+  return cc_intrinsics_optimize_views_huber(opt, device, F, uv_views, xyz_views, counts, intr9, mask, q, t, summary, 0.0);
+}
+
+}  // extern "C"

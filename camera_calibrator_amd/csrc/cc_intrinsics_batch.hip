@@ -630,30 +630,29 @@ static void batch_destroy(cc_intrinsics_batch* h) {
 static int batch_create_impl(cc_intrinsics_batch* h, const int64_t* frame_offsets, const float* uv, const float* xyz, size_t extra_bytes, bool wait) {
   const size_t B = (size_t)h->B, F = (size_t)h->Ftot, n1 = (size_t)std::max<int64_t>(h->N, 1);
   if (int rc = stream_get(h->device, &h->stream)) return rc;
-  size_t cursor = 0;
-  auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_intr = take(B * 32 * sizeof(double));
-  const size_t o_pose = take(2 * F * 8 * sizeof(double));
-  const size_t o_stats = take(F * kStatsCols * sizeof(double));
-  const size_t o_hd0 = take(F * 16 * sizeof(double));
-  const size_t o_sp = take(F * 8 * sizeof(double));
-  const size_t o_Y = take(F * kYStride * sizeof(double));
-  const size_t o_ds = take(B * 16 * sizeof(double));
-  const size_t o_ss = take(B * 16 * sizeof(double));
-  const size_t o_ctl = take(B * sizeof(LmCtl));
-  const size_t o_opts = take(sizeof(LmOpts));
-  const size_t o_mask = take(B * sizeof(uint32_t));
-  const size_t o_huber = take(B * sizeof(double));
-  const size_t zeroed = cursor;   // everything above starts as zeros
-  const size_t o_blocks = take(2 * F * 256 * sizeof(double));
-  const size_t o_log = take((size_t)kBatchLogCap * B * sizeof(cc_iteration));
-  const size_t o_uv = take(n1 * 2 * sizeof(float));
-  const size_t o_xyz = take(n1 * 3 * sizeof(float));
-  const size_t o_off = take((F + 1) * sizeof(int64_t));
-  const size_t o_where = take(F * 2 * sizeof(int32_t));
-  const size_t o_first = take((B + 1) * sizeof(int32_t));
-  const size_t o_extra = take(extra_bytes);
-  if (int rc = arena_get(h->device, cursor, &h->arena, &h->arena_cached)) return rc;
+  ArenaCursor cur;
+  const size_t o_intr = cur.take(B * 32 * sizeof(double));
+  const size_t o_pose = cur.take(2 * F * 8 * sizeof(double));
+  const size_t o_stats = cur.take(F * kStatsCols * sizeof(double));
+  const size_t o_hd0 = cur.take(F * 16 * sizeof(double));
+  const size_t o_sp = cur.take(F * 8 * sizeof(double));
+  const size_t o_Y = cur.take(F * kYStride * sizeof(double));
+  const size_t o_ds = cur.take(B * 16 * sizeof(double));
+  const size_t o_ss = cur.take(B * 16 * sizeof(double));
+  const size_t o_ctl = cur.take(B * sizeof(LmCtl));
+  const size_t o_opts = cur.take(sizeof(LmOpts));
+  const size_t o_mask = cur.take(B * sizeof(uint32_t));
+  const size_t o_huber = cur.take(B * sizeof(double));
+  const size_t zeroed = cur.bytes;   // everything above starts as zeros
+  const size_t o_blocks = cur.take(2 * F * 256 * sizeof(double));
+  const size_t o_log = cur.take((size_t)kBatchLogCap * B * sizeof(cc_iteration));
+  const size_t o_uv = cur.take(n1 * 2 * sizeof(float));
+  const size_t o_xyz = cur.take(n1 * 3 * sizeof(float));
+  const size_t o_off = cur.take((F + 1) * sizeof(int64_t));
+  const size_t o_where = cur.take(F * 2 * sizeof(int32_t));
+  const size_t o_first = cur.take((B + 1) * sizeof(int32_t));
+  const size_t o_extra = cur.take(extra_bytes);
+  if (int rc = arena_get(h->device, cur.bytes, &h->arena, &h->arena_cached)) return rc;
   char* base = static_cast<char*>(h->arena);
   h->extra = extra_bytes ? base + o_extra : nullptr;
   CC_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->h_ctl), B * sizeof(LmCtl), hipHostMallocDefault));
@@ -892,18 +891,157 @@ int cc_intrinsics_batch_solve(cc_intrinsics_batch* h, const cc_options* opt, cc_
   return CC_OK;
 }
 
+}  // extern "C"
+
+// EXTENSION: the fisheye focal-length start for every problem of a batch, on a handle (cc_intrinsics_batch_estimate_start_fisheye,
+// cc_intrinsics_batch_start_scores; the one-shot pipeline below runs it too)
+#include "cc_intr_start_batch_host.hpp"
+
+// The one-shot calls (cc_intrinsics_batch_optimize, cc_intrinsics_batch_estimate and its _huber / _model / _start forms): one body
+// -- the checks, a handle, a start, set_state -> set_huber -> solve -> get_state -- and one filled-in BatchOneShot per entry point.
+namespace cc {
+
+struct BatchOneShot {
+  const char* who;                // the call's name in every message
+  const cc_options* opt;
+  int32_t device;
+  int64_t B;                      // n_problems
+  const int64_t *problem_offsets, *frame_offsets;
+  const float *uv, *xyz;
+  const uint32_t* const_mask;
+  double *intr9, *q, *t;          // CALLER: the start on entry; every start: the solution on return
+  cc_summary* summaries;          // (the public calls' arguments, in their order)
+  // The start: the caller's state; Zhang's closed form per problem on the handle's device arrays, K and poses rounded to float as
+  // cc_intrinsics_estimate hands them over; or the batched fisheye focal search (`search`).
+  enum Start { CALLER, ZHANG, FOCAL_SEARCH } start = CALLER;
+  const cc_intr_start_options* search = nullptr;
+  const double* distortion5 = nullptr;   // ZHANG / FOCAL_SEARCH: [B][5] where the distortion starts (NULL: zeros; fisheye: k1..k4, the fifth ignored)
+  float* K_init9 = nullptr;              // ... and [B][9] where the start's K goes (may be NULL)
+  const double* huber_a = nullptr;       // EXTENSION: [B] or NULL
+  int32_t model = CC_MODEL_RADTAN;       // EXTENSION: the camera model of the whole batch
+};
+
+// scratch of Zhang's initialisation, per frame: gram double[256] | H float[9] (padded to 12) | q float[4] | t float[3] (padded to 4);
+// per problem: K float[9] (padded to 64 bytes)
+constexpr size_t kBatchZhangPerFrame = 256 * sizeof(double) + 12 * sizeof(float) + 4 * sizeof(float) + 4 * sizeof(float), kBatchZhangPerProblem = 64;
+
+// Zhang per problem (zhang_on_device, the handle's stream): K_init9, intr9[p][0..3], q and t. Its wait covers the upload.
+static int batch_start_zhang(cc_intrinsics_batch* h, const BatchOneShot& a) {
+  const size_t B = (size_t)h->B, F = (size_t)h->Ftot;
+  double* dgram = reinterpret_cast<double*>(h->extra);
+  float* dH = reinterpret_cast<float*>(h->extra + F * 256 * sizeof(double));
+  float* dq = dH + F * 12;
+  float* dt = dq + F * 4;
+  float* dK = dt + F * 4;   // [B][16]
+  for (size_t p = 0; p < B; ++p) {
+    const int64_t f0 = a.problem_offsets[p], Fp = a.problem_offsets[p + 1] - f0;
+    if (int rc = zhang_on_device(h->stream, Fp, h->d.off + f0, h->d.uv, h->d.xyz, dgram + (size_t)f0 * 256, dH + (size_t)f0 * 9,
+                                 dK + p * 16, dq + (size_t)f0 * 4, dt + (size_t)f0 * 3)) return rc;
+  }
+  std::vector<float> Kf(B * 16), qf(F * 4), tf(F * 3);
+  CC_HIP(hipMemcpyAsync(Kf.data(), dK, Kf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipMemcpyAsync(qf.data(), dq, qf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipMemcpyAsync(tf.data(), dt, tf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  CC_HIP(hipStreamSynchronize(h->stream));   // (covers the upload: uv / xyz are the caller's)
+  for (size_t p = 0; p < B; ++p) {
+    const float* K9 = Kf.data() + p * 16;
+    if (a.K_init9) std::memcpy(a.K_init9 + p * 9, K9, 9 * sizeof(float));
+    double* k = a.intr9 + p * 9;
+    k[0] = K9[0]; k[1] = K9[4]; k[2] = K9[2]; k[3] = K9[5];
+  }
+  for (size_t i = 0; i < qf.size(); ++i) a.q[i] = qf[i];
+  for (size_t i = 0; i < tf.size(); ++i) a.t[i] = tf[i];
+  return CC_OK;
+}
+
+// The batched focal search in the arena's scratch (L): intr9[p][0..3], q and t are its picks, K_init9 those Ks. One host wait,
+// which covers the upload.
+static int batch_start_search(cc_intrinsics_batch* h, const BatchOneShot& a, const IntrStartBatchTables& tables, const IntrStartBatchLayout& L) {
+  IntrStartBatchOutcome outcome;
+  int rc = intr_start_batch_run(h, h->extra, tables, L, *a.search, a.who, a.intr9, a.q, a.t, nullptr, &outcome);
+  if (rc == CC_ERR_STATE) {   // (the data admit no start: the caller's arguments, not a state of a handle the caller has)
+    const std::string why = last_error();
+    rc = fail(CC_ERR_BAD_ARGUMENT, "%s", why.c_str());
+  }
+  if (rc) return rc;
+  if (outcome.invalid_problem >= 0)
+    return fail(CC_ERR_BAD_ARGUMENT, "%s: problem %lld: view %lld has no pose at any candidate focal length (fewer than 4 points, collinear points, or a non-finite pixel or point)",
+                a.who, (long long)outcome.invalid_problem, (long long)outcome.invalid_view);
+  if (a.K_init9)
+    for (int64_t p = 0; p < a.B; ++p) {
+      const double* k = a.intr9 + p * 9;
+      const float K9[9] = {(float)k[0], 0.0f, (float)k[2], 0.0f, (float)k[1], (float)k[3], 0.0f, 0.0f, 1.0f};
+      std::memcpy(a.K_init9 + p * 9, K9, sizeof(K9));
+    }
+  return CC_OK;
+}
+
+static int batch_one_shot(const BatchOneShot& a) {
+  const char* who = a.who;
+  const int64_t B = a.B;
+  // Which refusal wins when several apply belongs to each symbol as it is: the Zhang call names an unknown model ahead of a NaN
+  // threshold, the search call its model and its options behind one.
+  if (!a.intr9 || !a.q || !a.t) return fail(CC_ERR_BAD_ARGUMENT, "%s: intr9 / q / t are NULL", who);
+  if (a.start == BatchOneShot::ZHANG && a.model != CC_MODEL_RADTAN && a.model != CC_MODEL_FISHEYE)
+    return fail(CC_ERR_BAD_ARGUMENT, "%s: unknown model %d", who, (int)a.model);
+  if (a.huber_a)
+    for (int64_t p = 0; p < B; ++p)
+      if (a.huber_a[p] != a.huber_a[p]) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a[%lld] is NaN", who, (long long)p);
+  if (a.start == BatchOneShot::FOCAL_SEARCH) {
+    if (a.model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: the focal-length search is a start of the fisheye model (model %d)", who, (int)a.model);
+    if (int rc = intr_start_check(*a.search, who)) return rc;
+  }
+  IntrStartBatchTables tables;
+  IntrStartBatchLayout L(0, 0, 0, 0, 0);   // (the search's)
+  size_t per_frame = 0, per_problem = 0;   // the start's scratch, a part of the one-shot arena (batch_create sizes it per frame and per problem)
+  if (a.start != BatchOneShot::CALLER) {   // the start's preconditions, before any device call
+    std::vector<int32_t> first, where;
+    if (int rc = batch_build_tables(who, B, a.problem_offsets, a.frame_offsets, &first, &where)) return rc;
+    for (int64_t p = 0; p < B; ++p) {
+      if (a.problem_offsets[p + 1] - a.problem_offsets[p] < 3) return fail(CC_ERR_BAD_ARGUMENT, "%s: problem %lld has fewer than 3 frames", who, (long long)p);
+      for (int64_t f = a.problem_offsets[p]; a.start == BatchOneShot::ZHANG && f < a.problem_offsets[p + 1]; ++f)
+        if (a.frame_offsets[f + 1] - a.frame_offsets[f] < 4) return fail(CC_ERR_BAD_ARGUMENT, "%s: frame %lld has fewer than 4 points", who, (long long)f);
+    }
+    if (a.start == BatchOneShot::ZHANG) {
+      per_frame = kBatchZhangPerFrame; per_problem = kBatchZhangPerProblem;
+    } else {
+      intr_start_batch_tables(B, a.problem_offsets, a.frame_offsets, a.search->search_views, &tables);
+      L = IntrStartBatchLayout(B, a.problem_offsets[B], tables.searched[(size_t)B], (int64_t)tables.extent.size(), a.search->candidates);
+      per_problem = (L.bytes + (size_t)B - 1) / (size_t)B;
+    }
+  }
+  cc_intrinsics_batch* h = nullptr;
+  // (the caller's state needs no start whose wait would cover the upload: the handle's creation waits for it, as it always has)
+  if (int rc = batch_create(who, a.device, B, a.problem_offsets, a.frame_offsets, a.uv, a.xyz, per_frame, per_problem, a.start == BatchOneShot::CALLER, &h)) return rc;
+  struct Guard { cc_intrinsics_batch* h; ~Guard() { batch_destroy(h); } } guard{h};
+  h->model = a.model;   // (a fresh handle: no state yet)
+  if (a.start != BatchOneShot::CALLER) {
+    if (int rc = a.start == BatchOneShot::ZHANG ? batch_start_zhang(h, a) : batch_start_search(h, a, tables, L)) {
+      (void)hipStreamSynchronize(h->stream);   // (uv / xyz are the caller's: nothing of them is in flight when the call returns)
+      return rc;
+    }
+    for (int64_t p = 0; p < B; ++p) {   // the distortion starts from the caller's
+      double* k = a.intr9 + p * 9;
+      for (int i = 0; i < 5; ++i) k[4 + i] = a.distortion5 ? a.distortion5[p * 5 + i] : 0.0;
+      if (a.model == CC_MODEL_FISHEYE) k[8] = 0.0;
+    }
+  }
+  int rc = cc_intrinsics_batch_set_state(h, a.intr9, a.const_mask, a.q, a.t);
+  if (!rc && a.huber_a) rc = cc_intrinsics_batch_set_huber(h, a.huber_a);
+  if (!rc) rc = cc_intrinsics_batch_solve(h, a.opt, a.summaries);
+  if (!rc) rc = cc_intrinsics_batch_get_state(h, a.intr9, a.q, a.t);
+  return rc;
+}
+
+}  // namespace cc
+
+extern "C" {
+
 int cc_intrinsics_batch_optimize(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
                                  const int64_t* frame_offsets, const float* uv, const float* xyz, double* intr9,
                                  const uint32_t* const_mask, double* q, double* t, cc_summary* summaries) {
-  using namespace cc;
-  if (!intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "cc_intrinsics_batch_optimize: intr9 / q / t are NULL");
-  cc_intrinsics_batch* h = nullptr;
-  if (int rc = batch_create("cc_intrinsics_batch_optimize", device, n_problems, problem_offsets, frame_offsets, uv, xyz, 0, 0, true, &h)) return rc;
-  int rc = cc_intrinsics_batch_set_state(h, intr9, const_mask, q, t);
-  if (!rc) rc = cc_intrinsics_batch_solve(h, opt, summaries);
-  if (!rc) rc = cc_intrinsics_batch_get_state(h, intr9, q, t);
-  batch_destroy(h);
-  return rc;
+  const cc::BatchOneShot a{"cc_intrinsics_batch_optimize", opt, device, n_problems, problem_offsets, frame_offsets, uv, xyz, const_mask, intr9, q, t, summaries};
+  return cc::batch_one_shot(a);
 }
 
 // Calibrator::Estimate for every problem of the batch: Zhang's closed-form initialisation per problem on the handle's
@@ -917,59 +1055,8 @@ int cc_intrinsics_batch_estimate_model(const cc_options* opt, int32_t device, in
                                        const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
                                        const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
                                        const double* huber_a, int32_t model) {
-  using namespace cc;
-  const char* who = "cc_intrinsics_batch_estimate";
-  if (!intr9 || !q || !t) return fail(CC_ERR_BAD_ARGUMENT, "%s: intr9 / q / t are NULL", who);
-  if (model != CC_MODEL_RADTAN && model != CC_MODEL_FISHEYE) return fail(CC_ERR_BAD_ARGUMENT, "%s: unknown model %d", who, (int)model);
-  if (huber_a)
-    for (int64_t p = 0; p < n_problems; ++p)
-      if (huber_a[p] != huber_a[p]) return fail(CC_ERR_BAD_ARGUMENT, "%s: huber_a[%lld] is NaN", who, (long long)p);
-  {   // the Zhang preconditions, before any device call
-    std::vector<int32_t> first, where;
-    if (int rc = batch_build_tables(who, n_problems, problem_offsets, frame_offsets, &first, &where)) return rc;
-    for (int64_t p = 0; p < n_problems; ++p) {
-      if (problem_offsets[p + 1] - problem_offsets[p] < 3) return fail(CC_ERR_BAD_ARGUMENT, "%s: problem %lld has fewer than 3 frames", who, (long long)p);
-      for (int64_t f = problem_offsets[p]; f < problem_offsets[p + 1]; ++f)
-        if (frame_offsets[f + 1] - frame_offsets[f] < 4) return fail(CC_ERR_BAD_ARGUMENT, "%s: frame %lld has fewer than 4 points", who, (long long)f);
-    }
-  }
-  // scratch per frame: gram double[256] | H float[9] (padded to 12) | q float[4] | t float[3] (padded to 4); per problem: K float[9] (padded to 64 bytes)
-  const size_t per_frame = 256 * sizeof(double) + 12 * sizeof(float) + 4 * sizeof(float) + 4 * sizeof(float), per_problem = 64;
-  cc_intrinsics_batch* h = nullptr;
-  if (int rc = batch_create(who, device, n_problems, problem_offsets, frame_offsets, uv, xyz, per_frame, per_problem, false, &h)) return rc;
-  struct Guard { cc_intrinsics_batch* h; ~Guard() { batch_destroy(h); } } guard{h};
-  h->model = model;   // (a fresh handle: no state yet)
-  const size_t B = (size_t)h->B, F = (size_t)h->Ftot;
-  double* dgram = reinterpret_cast<double*>(h->extra);
-  float* dH = reinterpret_cast<float*>(h->extra + F * 256 * sizeof(double));
-  float* dq = dH + F * 12;
-  float* dt = dq + F * 4;
-  float* dK = dt + F * 4;   // [B][16]
-  for (size_t p = 0; p < B; ++p) {
-    const int64_t f0 = problem_offsets[p], Fp = problem_offsets[p + 1] - f0;
-    if (int rc = zhang_on_device(h->stream, Fp, h->d.off + f0, h->d.uv, h->d.xyz, dgram + (size_t)f0 * 256, dH + (size_t)f0 * 9,
-                                 dK + p * 16, dq + (size_t)f0 * 4, dt + (size_t)f0 * 3)) return rc;
-  }
-  std::vector<float> Kf(B * 16), qf(F * 4), tf(F * 3);
-  CC_HIP(hipMemcpyAsync(Kf.data(), dK, Kf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  CC_HIP(hipMemcpyAsync(qf.data(), dq, qf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  CC_HIP(hipMemcpyAsync(tf.data(), dt, tf.size() * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  CC_HIP(hipStreamSynchronize(h->stream));   // (covers the upload: uv / xyz are the caller's)
-  for (size_t p = 0; p < B; ++p) {
-    const float* K9 = Kf.data() + p * 16;
-    if (K_init9) std::memcpy(K_init9 + p * 9, K9, 9 * sizeof(float));
-    double* k = intr9 + p * 9;
-    k[0] = K9[0]; k[1] = K9[4]; k[2] = K9[2]; k[3] = K9[5];
-    for (int i = 0; i < 5; ++i) k[4 + i] = distortion5 ? distortion5[p * 5 + i] : 0.0;
-    if (model == CC_MODEL_FISHEYE) k[8] = 0.0;
-  }
-  for (size_t i = 0; i < qf.size(); ++i) q[i] = qf[i];
-  for (size_t i = 0; i < tf.size(); ++i) t[i] = tf[i];
-  int rc = cc_intrinsics_batch_set_state(h, intr9, const_mask, q, t);
-  if (!rc && huber_a) rc = cc_intrinsics_batch_set_huber(h, huber_a);
-  if (!rc) rc = cc_intrinsics_batch_solve(h, opt, summaries);
-  if (!rc) rc = cc_intrinsics_batch_get_state(h, intr9, q, t);
-  return rc;
+  return cc_intrinsics_batch_estimate_start(opt, device, n_problems, problem_offsets, frame_offsets, uv, xyz, distortion5, const_mask,
+                                            K_init9, intr9, q, t, summaries, huber_a, model, nullptr);
 }
 
 int cc_intrinsics_batch_estimate_huber(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
@@ -987,8 +1074,18 @@ int cc_intrinsics_batch_estimate(const cc_options* opt, int32_t device, int64_t 
                                             K_init9, intr9, q, t, summaries, nullptr);
 }
 
-}  // extern "C"
+// EXTENSION: cc_intrinsics_batch_estimate_model with the start chosen: NULL -> that call (Zhang, under its name and its checks); else
+// the focal search on the fisheye model
+int cc_intrinsics_batch_estimate_start(const cc_options* opt, int32_t device, int64_t n_problems, const int64_t* problem_offsets,
+                                       const int64_t* frame_offsets, const float* uv, const float* xyz, const double* distortion5,
+                                       const uint32_t* const_mask, float* K_init9, double* intr9, double* q, double* t, cc_summary* summaries,
+                                       const double* huber_a, int32_t model, const cc_intr_start_options* start) {
+  cc::BatchOneShot a{start ? "cc_intrinsics_batch_estimate_start" : "cc_intrinsics_batch_estimate", opt, device, n_problems, problem_offsets, frame_offsets,
+                     uv, xyz, const_mask, intr9, q, t, summaries};
+  a.start = start ? cc::BatchOneShot::FOCAL_SEARCH : cc::BatchOneShot::ZHANG;
+  a.search = start;
+  a.distortion5 = distortion5; a.K_init9 = K_init9; a.huber_a = huber_a; a.model = model;
+  return cc::batch_one_shot(a);
+}
 
-// EXTENSION: the fisheye focal-length start for every problem of a batch (cc_intrinsics_batch_estimate_start_fisheye,
-// cc_intrinsics_batch_start_scores, cc_intrinsics_batch_estimate_start)
-#include "cc_intr_start_batch_host.hpp"
+}  // extern "C"

@@ -2035,9 +2035,7 @@ int cc_rig_optimize(const cc_options* opt, int32_t device, int64_t C, int64_t F,
   hp.mark("create");
   rc = cc_rig_set_state(h, cam_q, cam_t, frame_q, frame_t);
   hp.mark("set_state");
-  cc_options o;
-  if (opt) o = *opt; else { cc_options_init(&o); o.max_iterations = 1000; }  // extrinsics_calibrator.cpp:211
-  o.use_graph = 0;   // one solve per handle: capturing and instantiating a graph cannot pay off
+  const cc_options o = cc::one_shot_options(opt, 1000);
   if (!rc) rc = cc_rig_solve(h, &o, summary);
   hp.mark("solve");
   if (!rc) rc = cc_rig_get_state(h, cam_q, cam_t, frame_q, frame_t, obs_cost);
@@ -2058,9 +2056,7 @@ int cc_rig_estimate(const cc_options* opt, int32_t device, int64_t C, int64_t F,
   int rc = cc_rig_create(device, C, F, n_world, off, obs_cam, obs_world, obs_uv, world_xyz, cam_frozen, huber_a, &h);
   if (rc) return rc;
   rc = cc_rig_estimate_start(h, nullptr, cam_q, cam_t, frame_q, frame_t, nullptr);
-  cc_options o;
-  if (opt) o = *opt; else { cc_options_init(&o); o.max_iterations = 1000; }
-  o.use_graph = 0;
+  const cc_options o = cc::one_shot_options(opt, 1000);
   if (!rc) rc = cc_rig_solve(h, &o, summary);
   if (!rc) rc = cc_rig_get_state(h, cam_q, cam_t, frame_q, frame_t, obs_cost);
   cc_rig_destroy(h);
@@ -2091,9 +2087,7 @@ int cc_rig_optimize_columns(const cc_options* opt, int32_t device, int64_t C, in
   if (rc) return rc;
   hp.mark("create");
   rc = cc_rig_set_state(h, cam_q, cam_t, frame_q, frame_t);
-  cc_options o;
-  if (opt) o = *opt; else { cc_options_init(&o); o.max_iterations = 1000; }  // extrinsics_calibrator.cpp:211
-  o.use_graph = 0;
+  const cc_options o = one_shot_options(opt, 1000);
   if (!rc) rc = cc_rig_solve(h, &o, summary);
   hp.mark("solve");
   if (!rc) rc = cc_rig_get_state(h, cam_q, cam_t, frame_q, frame_t, nullptr);
@@ -2231,9 +2225,7 @@ int cc_rig_optimize_multi(const cc_options* opt, int32_t n_devices, const int32_
     const int64_t f0 = first[(size_t)r];
     rc = cc_rig_set_state(hs[(size_t)r], cam_q, cam_t, frame_q + 4 * f0, frame_t + 3 * f0);
   }
-  cc_options o;
-  if (opt) o = *opt; else { cc_options_init(&o); o.max_iterations = 1000; }  // extrinsics_calibrator.cpp:211
-  o.use_graph = 0;
+  const cc_options o = one_shot_options(opt, 1000);
   std::vector<RigRun> runs((size_t)n);
   for (int r = 0; r < n && !rc; ++r) rc = rig_begin(hs[(size_t)r], &o, &runs[(size_t)r]);
   for (int chunk = 0; !rc; ++chunk) {

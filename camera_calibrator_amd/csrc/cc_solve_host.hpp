@@ -198,6 +198,29 @@ static int begin_common(SolveHost* h, const cc_options* opt, int log_cap, SolveR
   return 0;
 }
 
+// The options of a one-shot call (a handle made for ONE solve): the caller's, or the defaults -- the rig calls default to the
+// reference's 1000 iterations (extrinsics_calibrator.cpp:211) -- and in either case no graph.
+static cc_options one_shot_options(const cc_options* opt, int default_max_iterations = 0) {
+  cc_options o;
+  if (opt) o = *opt; else cc_options_init(&o);
+  if (!opt && default_max_iterations) o.max_iterations = default_max_iterations;
+  o.use_graph = 0;   // one solve per handle: capturing and instantiating a graph cannot pay off
+  return o;
+}
+
+// The phases of a one-shot call for cc_last_call_timing (include/cc_solver.h: [0] handle + device arena, [1] upload, [2] the
+// start, [3] solve, [4] read-back + teardown): every slot starts at 0 and mark(slot) adds the time since the last mark to it.
+struct PhaseClock {
+  double* tm = last_timing();
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  PhaseClock() { for (int i = 0; i < 5; ++i) tm[i] = 0.0; }
+  void mark(int slot) {
+    const auto t1 = std::chrono::steady_clock::now();
+    tm[slot] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    t0 = t1;
+  }
+};
+
 // The options are uploaded when they change, not per solve. true: the device must get `lo` (the caller stages the bytes its
 // own way and sets opts_valid once they are on their way).
 static bool opts_changed(SolveHost* h, const LmOpts& lo) {

@@ -35,18 +35,17 @@ extern "C" int cc_zhang_init(int32_t device, int64_t F, const int64_t* off, cons
   if (!uv || !xyz) return fail(CC_ERR_BAD_ARGUMENT, "cc_zhang_init: NULL arrays");
   if (int rc = select_device(device)) return rc;
   // one scratch arena (one hipMalloc / hipFree per call), 256-byte aligned pieces
-  size_t cursor = 0;
-  auto take = [&](size_t bytes) { const size_t at = cursor; cursor += (bytes + 255) & ~(size_t)255; return at; };
-  const size_t o_uv = take((size_t)N * 2 * sizeof(float)), o_xyz = take((size_t)N * 3 * sizeof(float));
-  const size_t o_off = take((size_t)(F + 1) * sizeof(int64_t)), o_gram = take((size_t)F * 256 * sizeof(double));
-  const size_t o_H = take((size_t)F * 9 * sizeof(float)), o_K = take(9 * sizeof(float));
-  const size_t o_q = take((size_t)F * 4 * sizeof(float)), o_t = take((size_t)F * 3 * sizeof(float));
+  ArenaCursor cur;
+  const size_t o_uv = cur.take((size_t)N * 2 * sizeof(float)), o_xyz = cur.take((size_t)N * 3 * sizeof(float));
+  const size_t o_off = cur.take((size_t)(F + 1) * sizeof(int64_t)), o_gram = cur.take((size_t)F * 256 * sizeof(double));
+  const size_t o_H = cur.take((size_t)F * 9 * sizeof(float)), o_K = cur.take(9 * sizeof(float));
+  const size_t o_q = cur.take((size_t)F * 4 * sizeof(float)), o_t = cur.take((size_t)F * 3 * sizeof(float));
   char* arena = nullptr;
   struct Release {  // frees the scratch arena on every exit path
     char** p;
     ~Release() { if (*p) hipFree(*p); }
   } release{&arena};
-  CC_HIP(hipMalloc(&arena, cursor));
+  CC_HIP(hipMalloc(&arena, cur.bytes));
   float* duv = reinterpret_cast<float*>(arena + o_uv);
   float* dxyz = reinterpret_cast<float*>(arena + o_xyz);
   int64_t* doff = reinterpret_cast<int64_t*>(arena + o_off);
